@@ -21,9 +21,12 @@ World>1 : one process per GPU.  On one node the gradient exchange is the P2P xGM
           rank uses RCCL all-reduce instead; config.allreduce says which path ran.  After the
           timed region the fp32 weights are checked bit-identical across ranks.
 
-Also measures the Chicago-taxi wide&deep trainer (steps/sec) unless --no-taxi.
+A plain run sets up, warms up, times --steps steps and prints one JSON line.  --full also measures the
+Chicago-taxi wide&deep trainer (steps/sec, "chicago_taxi" in the JSON line) unless --no-taxi.
+--dump-outputs DIR writes what the last timed step returned (loss, correct, count) and the fp32 weights it
+left as DIR/<name>.npy (float32, rank 0); the seeds are fixed, so the same arguments give the same inputs.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no rank environment the
+Launch: python bench.py [--gpus N --steps K --warmup W --full --dump-outputs DIR].  With N > 1 and no rank environment the
 script launches its own N ranks (parallel/launch.py: one process per GPU, torchrun's env contract;
 refuses when fewer than N GPUs are visible unless --rehearse, which shares devices / uses the CPU
 with gloo); under torch.distributed.run it is one of the ranks.  n_gpus is the size of the process
@@ -51,8 +54,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch-per-gpu", type=int, default=int(os.environ.get("HOPSX_BENCH_BATCH", "32")))
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-taxi", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the Chicago-taxi wide&deep trainer (a run of its own after the headline one)")
+    ap.add_argument("--no-taxi", action="store_true", help="with --full: skip the taxi trainer all the same")
     ap.add_argument("--taxi-batch", type=int, default=40)  # TFX taxi trainer batch
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and the weights it left as DIR/<name>.npy")
     ap.add_argument("--rehearse", action="store_true",
                     help="allow more ranks than GPUs (ranks share devices, gloo process group)")
     return ap.parse_args()
@@ -76,6 +83,24 @@ def timed(step_fn, n, sync_dev):
     hdist.barrier()
     el = time.perf_counter() - t0
     return hdist.all_reduce_scalar(el, "max")
+
+
+def dump_outputs(path, result, model):
+    """What a caller of the timed path holds after its last step, one float32 ``<name>.npy`` each: the
+    step's returned loss / correct / count and every parameter as that step's update left it (fp32
+    master weights, ``param.<name>``; 1.39 M values, 5.6 MB in all)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+
+    def f32(v):
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    arrays = {k: f32(result[k]) for k in ("loss", "correct", "count") if result.get(k) is not None}
+    arrays.update({f"param.{n}": f32(p) for n, p in model.named_parameters()})
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def main():
@@ -179,6 +204,8 @@ def main():
     loss = float(out["r"]["loss"].item())
     ms = el / a.steps * 1e3
     ips = B * world * a.steps / el
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out["r"], model)  # (the data-parallel replicas are checked identical below)
     replicas = None
     dp_path = dp.path if dp is not None else None
     ranks = None
@@ -193,7 +220,7 @@ def main():
         dp.close()  # collective; raises if a P2P collective failed during the run
 
     taxi = None
-    if not a.no_taxi:
+    if a.full and not a.no_taxi:
         try:
             from hops_examples_amd.models.widedeep import bench_taxi
 

@@ -535,6 +535,9 @@ def main():
     dev = hdist.device()
     torch.manual_seed(1234 + rank)
     CONFIGS[a.config](a, dev, rank, world)
+    # the ordered teardown bench.py ends with (a no-op after a config that shut down itself): a rank that left
+    # its process group to interpreter teardown could abort there ("terminate called without an active exception")
+    hdist.shutdown()
     launch.rank_exit(0)  # a finished rank of the self-launch skips interpreter teardown (see launch.rank_exit)
 
 

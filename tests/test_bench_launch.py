@@ -41,6 +41,28 @@ def test_bench_self_launches_two_ranks():
     assert rec["dtype"] == "fp32" and rec["config"]["hipgraph"] is False  # honest about the CPU run
 
 
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run times the headline steps only (no taxi trainer) and, with --dump-outputs, leaves what the
+    last timed step returned and the weights after it as float32 .npy files (same seeds -> same arrays)."""
+    import numpy as np
+
+    def run(d):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return _json_line(r.stdout), {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+
+    rec, a = run(tmp_path / "a")
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["chicago_taxi"] is None
+    assert {"loss", "correct", "count", "param.conv1.weight", "param.fc2.bias"} <= set(a)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.size for k, v in a.items() if k.startswith("param.")) == 1_394_282
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
+    assert abs(float(a["loss"].reshape(-1)[0]) - rec["final_loss"]) < 1e-3
+    _, b = run(tmp_path / "b")
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_bench_refuses_more_ranks_than_gpus():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-taxi"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)

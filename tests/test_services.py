@@ -11,7 +11,8 @@ from pathlib import Path
 import pandas as pd
 import pytest
 
-SACRAMENTO = Path("/root/reference/notebooks/featurestore/aws/data/Sacramentorealestatetransactions.csv")
+# the reference's notebooks/featurestore/aws/data file, shipped with the tests (see test_fixtures.py)
+SACRAMENTO = Path(__file__).resolve().parent / "fixtures" / "Sacramentorealestatetransactions.csv"
 
 
 def _prog(project_root, name, body):
@@ -111,7 +112,6 @@ def test_dag_job_chain_and_failure_propagation(project_root):
     assert dag2.run() == {"a": "failed", "b": "upstream_failed"}
 
 
-@pytest.mark.skipif(not SACRAMENTO.exists(), reason="reference fixture missing")
 def test_hive_external_to_partitioned_orc(project_root):
     from hops_examples_amd import hive
 

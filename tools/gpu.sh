@@ -45,7 +45,7 @@ case $job in
 verify)
   T=900 pyt $out/pytest_gpu.log tests -m gpu
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || fail $out/smoke.log
-  bench bench bench.py --steps 20 --warmup 5
+  bench bench bench.py --steps 20 --warmup 5 --full
   [ "$1" = quick ] && exit 0
   bench cifar20 benchmarks/run.py cifar_resnet --depth 20 --batch 128 --steps 100 --warmup 10
   bench r50_b64 benchmarks/run.py resnet50 --batch 64 --steps 30 --warmup 5
@@ -61,7 +61,7 @@ taxi)
   timeout -k 10 180 python -u tools/taxi_phases.py > $out/phases.txt 2>&1 || fail $out/phases.txt
   cat $out/phases.txt
   bench taxi benchmarks/run.py taxi --steps 200 --warmup 20
-  bench bench bench.py --steps 20 --warmup 5 ;;
+  bench bench bench.py --steps 20 --warmup 5 --full ;;
 data)
   T=400 bench ingest benchmarks/run.py titanic_ingest --rows 50000000
   bench titanic benchmarks/run.py titanic --rows 891000 --steps 300 --warmup 20
