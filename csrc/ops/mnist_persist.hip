@@ -37,6 +37,10 @@
 // rows and advanced by nsteps at the end of each launch), so no memset precedes a launch.  Every
 // poll is bounded (wall clock) and also watches a sticky error word, so a fault drains the grid.
 // Payload buffers are double-buffered by step parity.
+// B towards the positions is the exception (the slowest hop in the flag form: 201 workgroups on one flag
+// line, a drain in the producer, a second round trip in the consumer): each head also stores dh as 64
+// 8-byte {bf16 pair, epoch} granules that are their own flag (G16 R2, "tagged granules" below), and the
+// positions wait on those tags; the fp32 payload + FL_B flag stay for the heads' own fc2 update.
 //
 // Determinism: no float atomics anywhere — every cross-workgroup sum is a fixed-order loop, so two
 // runs from the same state are bit-identical.
@@ -63,6 +67,16 @@ constexpr int FL_EPOCH = FL_WORDS - 2;  // 64-bit epoch base after the flag rows
 // small fp32 parameters [b2 | conv1 w | conv1 b]
 constexpr int D_F32 = OFF_B2 * 2;                 // byte offset of the fp32 part
 constexpr int D_BYTES = D_F32 + (NCONV - OFF_B2) * 4;
+// Tagged hand-off B (dh for the positions): 8-byte granules {value, tag = the step's epoch} that are their own
+// flag (cdna_hip_programming §6 G16 R2), each written by ONE 8-byte write-through store and read by 8-byte
+// sc1 loads, double-buffered by step parity: [2][32 images][64] {bf16 dh[2l] | bf16 dh[2l+1] << 16, tag}.
+// They live behind the flag rows in the flag allocation (zeroed with it: a tag of 0 is never an epoch).
+// (The same form for D, the conv parameters, measured SLOWER than its flag form — 26.4 vs 25.6 us/step: D's
+// hop is hidden behind the fc1 Adadelta, and 34 KB of 8-byte loads per reader cost more than the poll + 17 KB
+// of 16-byte loads they replace; profiles/r7_persist_tagged.txt.)
+constexpr int TGB_N = NHEAD * (HID / 2);  // 2048 granules (16 KB) per parity
+constexpr int TG_WORDS = 2 * 2 * TGB_N;   // 32-bit words of the tag region
+static_assert(FL_WORDS % 2 == 0 && TGB_N % 256 == 0, "granules are 8-B aligned; every thread owns TGB_N / 256");
 
 // LDS row strides (bf16 elements), padded by 16 B against bank conflicts of the fragment reads
 constexpr int W1S = 72, W2S = 136, C1S = 40, PLS = 72, DHS = 136, DCS = 136;
@@ -120,6 +134,7 @@ static_assert(NRED * 13 <= 256 && NSLICE * SLICE >= NCONV && NSLICE <= NPOS, "sl
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned __attribute__((address_space(1))) gu32;
+typedef unsigned long long __attribute__((address_space(1))) gu64;
 
 struct Args {
   float* master;      // arena fp32 parameters
@@ -138,7 +153,8 @@ struct Args {
   float* slabB;  // [2][32][PAY]
   float* slabC;  // [2][169][NCONV]
   float* slabD;  // [2][D_BYTES / 4]
-  unsigned* flags;  // [FL_WORDS]: flag rows + the epoch base (zeroed once at allocation)
+  unsigned* flags;  // [FL_WORDS + TG_WORDS]: flag rows + the epoch base, then the tag granules (zeroed once
+                    // at allocation)
   unsigned* err;    // sticky error word (0 = ok)
   float* out;       // [nsteps][2]: mean loss, correct count
   unsigned long long* dbg;  // optional [GRID][nsteps][16] wall-clock phase stamps
@@ -152,6 +168,11 @@ struct Args {
   int pollw, stagger;  // waves polling a hand-off wait and their start offsets (HOPSX_PERSIST_POLLW / _STAGGER)
   int pollw_a, pollw_b, pollw_c, pollw_d;  // per hand-off (HOPSX_PERSIST_POLLW_A.._D, default POLLW; C: 4)
   int head1w;          // 1: one wave computes the head from registers and publishes B (HOPSX_PERSIST_HEAD1W)
+  // hand-off form, one word (one scalar register for the whole launch): bit 0: the positions read dh (B) from
+  // tagged granules, not the flag form (HOPSX_PERSIST_TAGGED); bit 1: a flag poll loads the error word with
+  // its flags, one round trip (HOPSX_PERSIST_POLL1); bits 8..: heads whose tag opens the B wait's gate
+  // (HOPSX_PERSIST_GATE)
+  int hand;
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
   // data parallel (DP instantiation)
   int world, rank;
@@ -214,8 +235,12 @@ __device__ __forceinline__ int xslot(const Args& a, int peer) { return a.loopbac
 // detection delay shrinks from ~half a poll round trip toward ~half of that over pollw.  The first
 // wave to see every flag (or the error) tells the others through the LDS word s_ok[1], set to this
 // wait's `code` (unique per phase and step, never 0); s_ok[0] carries the verdict as before.
+// poll1 (HOPSX_PERSIST_POLL1): the error word is loaded WITH the flags of the same iteration (one wait for
+// both), so a poll iteration is one memory round trip instead of two dependent ones; the flags are still
+// judged first, so a hand-off that has arrived wins over an error raised meanwhile, as before.
 __device__ __forceinline__ bool wait_all(const unsigned* flags, int n, unsigned epoch, unsigned* err, unsigned code,
-                                      int acquire, int* s_ok, long long tmo, int pollw = 1, int stagger = 0) {
+                                      int acquire, int* s_ok, long long tmo, int pollw = 1, int stagger = 0,
+                                      int poll1 = 0) {
   if (pollw <= 1) {
     if (threadIdx.x < 64) {
       const int lane = threadIdx.x;
@@ -223,9 +248,11 @@ __device__ __forceinline__ bool wait_all(const unsigned* flags, int n, unsigned 
       const long long t0 = wall_clock64();
       for (unsigned spins = 0;; ++spins) {
         int ok = 1;
+        unsigned e = poll1 ? flag_load(err) : 0u;
         for (int k = lane; k < n; k += 64) ok &= flag_load(flags + k) == epoch;
         if (__all(ok)) break;
-        if (__builtin_amdgcn_readfirstlane(flag_load(err)) != 0u) {
+        if (!poll1) e = flag_load(err);
+        if (__builtin_amdgcn_readfirstlane(e) != 0u) {
           good = 0;
           break;
         }
@@ -257,6 +284,7 @@ __device__ __forceinline__ bool wait_all(const unsigned* flags, int n, unsigned 
     for (unsigned spins = 0;; ++spins) {
       if (__builtin_amdgcn_readfirstlane(*gen) == (int)code) break;  // another wave saw it
       int ok = 1;
+      unsigned e = poll1 ? flag_load(err) : 0u;
       for (int k = lane; k < n; k += 64) ok &= flag_load(flags + k) == epoch;
       if (__all(ok)) {
         if (lane == 0) {
@@ -265,7 +293,8 @@ __device__ __forceinline__ bool wait_all(const unsigned* flags, int n, unsigned 
         }
         break;
       }
-      if (__builtin_amdgcn_readfirstlane(flag_load(err)) != 0u) good = 0;
+      if (!poll1) e = flag_load(err);
+      if (__builtin_amdgcn_readfirstlane(e) != 0u) good = 0;
       if ((spins & 15u) == 15u && wall_clock64() - t0 > tmo) {
         if (lane == 0) atomicCAS(err, 0u, code);
         good = 0;
@@ -299,9 +328,11 @@ __device__ __forceinline__ bool wait_peers(const Args& a, int base, int stride, 
     const long long t0 = wall_clock64();
     for (unsigned spins = 0;; ++spins) {
       const bool mine = lane < a.world && lane != a.rank;
+      unsigned e = (a.hand & 2) ? flag_load(a.err) : 0u;
       const int ok = !mine || (int)(xflag_load(page + base + lane * stride) - epoch) >= 0;
       if (__all(ok)) break;
-      if (__builtin_amdgcn_readfirstlane(flag_load(a.err)) != 0u) {
+      if (!(a.hand & 2)) e = flag_load(a.err);
+      if (__builtin_amdgcn_readfirstlane(e) != 0u) {
         good = 0;
         break;
       }
@@ -369,6 +400,88 @@ __device__ __forceinline__ long conv_idx(const Args& a, int j) {
 
 __device__ __forceinline__ void stamp(const Args& a, int s, int ph) {
   if (a.dbg && threadIdx.x == 0) a.dbg[((long)blockIdx.x * a.nsteps + s) * 16 + ph] = (unsigned long long)wall_clock64();
+}
+
+// ---- tagged granules (hand-off B, heads -> positions): the data is the flag ----
+// ONE aligned 8-byte write-through (sc1) store per granule and lane: value in the low word, tag in the high
+__device__ __forceinline__ void granule_store(unsigned long long* g, unsigned epoch, unsigned value) {
+  __hip_atomic_store((gu64*)g, ((unsigned long long)epoch << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long granule_load(const unsigned long long* g) {
+  return __hip_atomic_load((gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_load_dwordx2 sc1
+}
+// The cheap first stage of the B wait (the positions wait ~7 us there: 169 workgroups sweeping 16 KB each
+// all that time would load the fabric).  Wave 0 polls ONE granule per head — lane l < 32 image l's granule
+// `gi`, 32 different lines — with s_sleep, until `need` of them carry the epoch; same error word, wall-clock
+// bound and uniform verdict as wait_all.  It only opens the sweep: the sweep checks every granule's tag.
+__device__ __forceinline__ bool gate_tags(const unsigned long long* g, int gi, unsigned epoch, int need, unsigned* err,
+                                       unsigned code, int* s_ok, long long tmo) {
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const bool mine = lane < NHEAD;
+    int good = 1;
+    const long long t0 = wall_clock64();
+    for (unsigned spins = 0;; ++spins) {
+      const unsigned e = flag_load(err);
+      const unsigned long long x = mine ? granule_load(g + lane * (HID / 2) + gi) : 0ull;
+      const bool hit = mine && (unsigned)(x >> 32) == epoch;
+      if (__popcll(__ballot(hit)) >= need) break;
+      if (__builtin_amdgcn_readfirstlane(e) != 0u) {
+        good = 0;
+        break;
+      }
+      if ((spins & 15u) == 15u && wall_clock64() - t0 > tmo) {
+        if (lane == 0) atomicCAS(err, 0u, code);
+        good = 0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (lane == 0) *s_ok = good;
+  }
+  __syncthreads();
+  const int v = *s_ok;
+  return v != 0;
+}
+// Every thread owns granules tid + 256 k (k < N) of g[0 .. 256 N): it loads them (all in flight, 8-byte sc1
+// loads to registers), hands the value of each whose tag is the epoch to put(index, value) and re-reads only
+// the others, until the whole workgroup has all of them; one barrier at the end (put writes LDS).  The error
+// word travels with each pass's loads (one round trip per pass); failure handling as wait_all, the verdict
+// through the LDS word s_fail (0 until a wave gives up), uniform.
+template <int N, class F>
+__device__ __forceinline__ bool sweep_tags(const unsigned long long* g, int tid, unsigned epoch, unsigned* err,
+                                        unsigned code, int* s_fail, long long tmo, F put) {
+  unsigned pend = (1u << N) - 1u;
+  unsigned long long x[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = granule_load(g + tid + 256 * k);  // the first pass: every granule
+  unsigned e = flag_load(err);
+  const long long t0 = wall_clock64();
+  for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      if (((pend >> k) & 1u) && (unsigned)(x[k] >> 32) == epoch) {
+        put(tid + 256 * k, (unsigned)x[k]);
+        pend &= ~(1u << k);
+      }
+    if (!__any(pend != 0u)) break;
+    bool bad = __builtin_amdgcn_readfirstlane(e) != 0u;
+    if (!bad && (spins & 15u) == 15u && wall_clock64() - t0 > tmo) {
+      if ((threadIdx.x & 63) == 0) atomicCAS(err, 0u, code);
+      bad = true;
+    }
+    if (bad) {
+      if ((threadIdx.x & 63) == 0) *s_fail = 1;
+      break;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      if ((pend >> k) & 1u) x[k] = granule_load(g + tid + 256 * k);
+    e = flag_load(err);
+  }
+  __syncthreads();
+  const int f = *s_fail;
+  return f == 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -618,8 +731,27 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     // ---- B: dh of all 32 images ----
     // (step 0: the heads run on this GPU only, so a B that has not come within tmo0 means workgroups of
     // this launch are not resident — fail fast with the co-residency code instead of waiting out tmo)
+    if (a.hand & 1) {
+      // tagged form: the heads' {bf16 dh pair, epoch} granules are the flag.  Wave 0 gates on one granule per
+      // head, then every thread sweeps its 8 granules straight into DH: no flag poll, no barrier between
+      // poll and load, no second L2 round trip, no fp32 -> bf16 conversion (the head made the same bits)
+      const unsigned long long* TB = (const unsigned long long*)(a.flags + FL_WORDS) + par * TGB_N;
+      const unsigned code = s ? ecode(2, s) : ecode(12, 0);
+      const long long tmo = s ? a.tmo : a.tmo0;
+      if (!gate_tags(TB, p & (HID / 2 - 1), ep, (a.hand >> 8), a.err, code, s_ok, tmo)) return;
+      if (!sweep_tags<TGB_N / 256>(TB, tid, ep, a.err, code, s_ok + 2, tmo, [&](int idx, unsigned v) {
+            *(unsigned*)(DH + (idx >> 6) * DHS + 2 * (idx & 63)) = v;
+          }))
+        return;
+      if constexpr (DP) {
+        drain();
+        __syncthreads();
+        if (tid < 64) raise_peers(a, XF_POOL + p, NPOS, gep);
+      }
+      stamp(a, s, 3);  // (the dh load is inside the wait in this form)
+    } else {
     if (!wait_all(a.flags + FL_B, NHEAD, ep, a.err, s ? ecode(2, s) : ecode(12, 0), a.acquire, s_ok,
-                  s ? a.tmo : a.tmo0, a.pollw_b, a.stagger))
+                  s ? a.tmo : a.tmo0, a.pollw_b, a.stagger, (a.hand & 2)))
       return;
     if constexpr (DP) {
       drain();
@@ -638,6 +770,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       }
     }
     __syncthreads();
+    }
     // ---- fc1 weight gradient (lane-owned layout) and input gradient ----
     f32x4 gw[2][4], dp[2];
     {
@@ -801,7 +934,8 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     stamp(a, s, 6);
     // ---- slice owners: fixed-order reduce of 52 params over the 169 partials, Adadelta, publish D ----
     if (owner) {
-      if (!wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger)) return;
+      if (!wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger, (a.hand & 2)))
+        return;
       stamp(a, s, 7);
       const int e0 = p * SLICE;
       if (tid < 13 * NRED) {
@@ -947,7 +1081,9 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     if (s + 1 < a.nsteps) draw_keep(s + 1);  // KEEP is next read after the D wait's barrier
     stamp(a, s, 9);
     // ---- D: the updated conv parameters for the next step ----
-    if (!wait_all(a.flags + FL_D, NSLICE, ep, a.err, ecode(4, s), a.acquire, s_ok, a.tmo, a.pollw_d, a.stagger)) return;
+    if (!wait_all(a.flags + FL_D, NSLICE, ep, a.err, ecode(4, s), a.acquire, s_ok, a.tmo, a.pollw_d, a.stagger,
+                  (a.hand & 2)))
+      return;
     stamp(a, s, 10);
     {
       const auto R = rsrc((const unsigned char*)a.slabD + (long)par * D_BYTES);
@@ -1067,7 +1203,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
     const int y = (int)a.ys[((cur0 + s) % a.nbatch) * B + i];
     // ---- A: reduce the 169 fc1 partial rows of image i (fixed order) ----
     if (!wait_all(a.flags + FL_A, NPOS, ep, a.err, s ? ecode(1, s) : ecode(12, 0), a.acquire, s_ok,
-                  s ? a.tmo : a.tmo0, a.pollw_a, a.stagger))
+                  s ? a.tmo : a.tmo0, a.pollw_a, a.stagger, (a.hand & 2)))
       return;
     stamp(a, s, 0);
     {
@@ -1131,6 +1267,11 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
           for (int c = 0; c < NCLS; ++c) d = fmaf(dl[c], HW[c * HID + n0 + u], d);
           dh[u] = h[u] > 0.f ? d : 0.f;
         }
+        // the tagged dh first (what the positions wait for): one 8-byte write-through store per lane, no drain
+        // in front of it; the fp32 payload + flag below serve the heads' fc2 update and the DP push
+        if (a.hand & 1)
+          granule_store((unsigned long long*)(a.flags + FL_WORDS) + (par * NHEAD + i) * (HID / 2) + lane, ep,
+                        (unsigned)f2bf(dh[0]) | ((unsigned)f2bf(dh[1]) << 16));
         const auto R = rsrc(a.slabB + ((long)par * NHEAD + i) * PAY);
         st_sc1x2(R, (PAY_DH + n0) * 4, dh[0], dh[1]);
         st_sc1x2(R, (PAY_H + n0) * 4, h[0], h[1]);
@@ -1189,7 +1330,10 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
       PAYL[PAY_H + tid] = h;
     }
     __syncthreads();
-    {  // publish B
+    {  // publish B (the tagged dh first, as in the one-wave form)
+      if ((a.hand & 1) && tid < HID / 2)
+        granule_store((unsigned long long*)(a.flags + FL_WORDS) + (par * NHEAD + i) * (HID / 2) + tid, ep,
+                      (unsigned)f2bf(PAYL[PAY_DH + 2 * tid]) | ((unsigned)f2bf(PAYL[PAY_DH + 2 * tid + 1]) << 16));
       const auto R = rsrc(a.slabB + ((long)par * NHEAD + i) * PAY);
       if (tid < PAY / 4) st_sc1(R, tid * 16, *(const f32x4*)(PAYL + tid * 4));
       drain();
@@ -1200,7 +1344,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
     stamp(a, s, 1);
     // ---- replicated fc2 / fc1-bias update from every image's payload ----
     if (!wait_all(a.flags + FL_B, NHEAD, ep, a.err, s ? ecode(5, s) : ecode(12, 0), a.acquire, s_ok,
-                  s ? a.tmo : a.tmo0, a.pollw, a.stagger))
+                  s ? a.tmo : a.tmo0, a.pollw, a.stagger, (a.hand & 2)))
       return;
     {
       const auto R = rsrc(a.slabB + (long)par * NHEAD * PAY);
@@ -1342,9 +1486,9 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
 template <bool DP>
 __global__ __launch_bounds__(256, 1) void mnist_persist_k(const Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int s_ok[2];  // [0] a wait's verdict, [1] the multi-wave wait's done word (wait_all)
+  __shared__ int s_ok[3];  // [0] a wait's verdict, [1] the multi-wave wait's done word (wait_all), [2] a sweep gave up
   stamp(a, 0, 13);  // (debug stamps: workgroup entry, before the launch prologue)
-  if (threadIdx.x == 0) s_ok[0] = s_ok[1] = 0;  // (read after the first barrier of either role)
+  if (threadIdx.x == 0) s_ok[0] = s_ok[1] = s_ok[2] = 0;  // (read after the first barrier of either role)
   const OptHP hp = load_hp(a.hp, a.hp_dev);
   const long long cur0 = a.cursor[0];
   const long long xs0 = DP ? a.xstep[0] : 0;
@@ -1360,6 +1504,7 @@ __global__ __launch_bounds__(256, 1) void mnist_persist_k(const Args a) {
 
 // ptrs: master shadow s1 s2 xs ys cursor rng step_dev hp_dev slabA slabB slabC slabD flags err out dbg(0 = none)
 //       [xstep xbuf[world] xflag[world]]   (world > 1: the data-parallel instantiation)
+//       flags: FL_WORDS + TG_WORDS 32-bit words, zeroed (geom[8] + geom[22]: the tag granules follow the flag rows)
 // iv:   off[8] nbatch salt nsteps batch acquire world rank loopback timeout_ms xfence
 // fv:   drop_p xscale xshift lr gscale wd rho eps
 static int g_persist_reload = 0;
@@ -1406,6 +1551,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.tmo0 = a.tmo;
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
+  static int kn_tagged, kn_gate, kn_poll1;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1432,6 +1578,16 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     // profiles/r6_persist_dp_sim.txt), so it is off by default
     kn_coop = (int)hopsx_env_int("HOPSX_PERSIST_COOP", 0);
     kn_start_ms = hopsx_env_int("HOPSX_PERSIST_START_MS", 50);
+    // the positions read dh from tagged granules instead of payload + drain + flag; HOPSX_PERSIST_TAGGED=0 is
+    // the flag form (25.2 -> 23.5 us/step: tools/persist_ab.py, profiles/r7_persist_tagged.txt).  _GATE: heads
+    // whose tag opens the B sweep (1, 4, 16, 24, 32 measured: 16 and 24 are 0.2-0.3 us/step faster than 1 and
+    // 32 — opened by the first head, every workgroup sweeps through the heads' skew; opened by the last, the
+    // sweep starts a poll period late).  _POLL1: the flag polls load the error word with the flags (one round
+    // trip per poll: 0.15 us/step)
+    kn_tagged = hopsx_env_int("HOPSX_PERSIST_TAGGED", 1) != 0;
+    const long gt = hopsx_env_int("HOPSX_PERSIST_GATE", NHEAD / 2);
+    kn_gate = (int)(gt >= 1 && gt <= NHEAD ? gt : NHEAD / 2);
+    kn_poll1 = hopsx_env_int("HOPSX_PERSIST_POLL1", 1) != 0;
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1442,6 +1598,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.pollw_c = kn_c;
   a.pollw_d = kn_d;
   a.head1w = kn_head1w;
+  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_gate << 8);
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;
   a.inv_gb = 1.f / (float)(world * B);
   if (dp) {
@@ -1524,4 +1681,5 @@ extern "C" void hopsx_mnist_persist_geom(long* g) {
   g[19] = XS_FC2;
   g[20] = XO_CONV;
   g[21] = XS_CONV;
+  g[22] = TG_WORDS;  // tag granules of hand-off B behind the flag rows (32-bit words)
 }

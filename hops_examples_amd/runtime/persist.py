@@ -52,7 +52,7 @@ def geometry() -> dict:
         g = _ext().mnist_persist_geom()
         _GEOM = dict(zip(["batch", "npos", "nhead", "grid", "nconv", "nslice", "slice", "pay", "flag_words",
                           "lds_bytes", "d_bytes", "x_bytes", "xflag_words", "max_ranks", "xo_pool", "xs_pool",
-                          "xo_dht", "xs_dht", "xo_fc2", "xs_fc2", "xo_conv", "xs_conv"], g))
+                          "xo_dht", "xs_dht", "xo_fc2", "xs_fc2", "xo_conv", "xs_conv", "tag_words"], g))
     return _GEOM
 
 
@@ -167,7 +167,11 @@ class PersistentMnistStep:
         self.slabB = torch.empty(2 * nh * g["pay"], **f32)
         self.slabC = torch.empty(2 * npos * g["nconv"], **f32)
         self.slabD = torch.empty(2 * g["d_bytes"] // 4, **f32)
-        self.flags = torch.zeros(g["flag_words"], device=dev, dtype=torch.int32)
+        # one zeroed allocation: the flag rows (+ epoch base), then the tag granules of the tagged hand-off B
+        # (the kernel finds them behind the flag rows; a tag of 0 is never an epoch)
+        self._flagbuf = torch.zeros(g["flag_words"] + g["tag_words"], device=dev, dtype=torch.int32)
+        self.flags = self._flagbuf[:g["flag_words"]]
+        self.tags = self._flagbuf[g["flag_words"]:]
         self.err = torch.zeros(4, device=dev, dtype=torch.int32)
         self.out = torch.zeros(2 * self.spl, **f32)
         self.cursor = torch.zeros(1, device=dev, dtype=torch.int64)
@@ -568,8 +572,9 @@ class PersistentMnistStep:
         e = int(self.err[0].item()) & 0xFFFFFFFF
         if e:
             # a launch that gave up left flag epochs behind without advancing the epoch base: clear them,
-            # so a later launch (after the caller resets err) cannot match a stale flag
-            self.flags.zero_()
+            # so a later launch (after the caller resets err) cannot match a stale flag; the same for the tags
+            # of the tagged hand-off
+            self._flagbuf.zero_()
             phase, step, wg = (e >> 24) & 0x7F, (e >> 12) & 0xFFF, e & 0xFFF
             if phase == 12:
                 raise PersistentError(f"mnist_persist: the grid's workgroups were not co-resident (workgroup {wg} "

@@ -57,7 +57,8 @@ def main():
     st.check()
     for s, v in res.items():
         med = statistics.median(v)
-        print(f"[{s}] median {med:.4f} ms/step ({32 / med * 1e3:,.0f} img/s)  min {min(v):.4f}  n={len(v)}")
+        # (5 decimals: the hand-off knobs differ by tenths of a microsecond per step, repeats by hundredths)
+        print(f"[{s}] median {med:.5f} ms/step ({32 / med * 1e3:,.0f} img/s)  min {min(v):.5f}  n={len(v)}")
 
 
 if __name__ == "__main__":

@@ -92,6 +92,10 @@ def timing(n, reps=5, loopback=0):
     def med(t, a, b):
         return (t[:, 1:, b] - t[:, 1:, a]).median().item()
 
+    # With the tagged B hand-off (HOPSX_PERSIST_TAGGED=1, the default) the positions sweep the dh granules
+    # straight into LDS inside the wait, so the dh load is part of the "wait B" row and the next row is the fc1
+    # wgrad/dgrad + pool bwd alone; with HOPSX_PERSIST_TAGGED=0 (flag form) the rows mean what they say
+
     rows = [("conv fwd (input, conv1, conv2 MFMA, pool, dropout)", pos, 0, 1), ("fc1 partial + publish A", pos, 1, 2),
             ("wait B (heads)", pos, 2, 3), ("dh load + fc1 wgrad/dgrad + pool bwd", pos, 3, 4),
             ("conv2 wgrad/dgrad + conv1 wgrad", pos, 4, 5), ("publish C", pos, 5, 6),
