@@ -72,6 +72,7 @@ extern "C" int hopsx_dbg_read_elementwise(unsigned* out);
 extern "C" int hopsx_dbg_read_rowreduce(unsigned* out);
 extern "C" int hopsx_dbg_read_wgrad_glds(unsigned* out);
 extern "C" int hopsx_dbg_read_embedding(unsigned* out);
+extern "C" int hopsx_dbg_read_mnist_eval(unsigned* out);
 
 // the debug build (-DHOPSX_DEBUG=1) is the module _hopsx_ops_dbg (same sources, hx_check compiled in)
 #ifndef HOPSX_MODNAME
@@ -161,6 +162,7 @@ HX_PYMOD(HOPSX_MODNAME) {
     {"rowreduce", hopsx_dbg_read_rowreduce},
     {"wgrad_glds", hopsx_dbg_read_wgrad_glds},
     {"embedding", hopsx_dbg_read_embedding},
+    {"mnist_eval", hopsx_dbg_read_mnist_eval},
     };
     std::vector<std::tuple<std::string, unsigned, unsigned, unsigned, unsigned>> out;
     for (const auto& t : tus) {
@@ -211,6 +213,11 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_mnist_persist(a.p.data(), (int)a.p.size(), a.iv.data(), (int)a.iv.size(), a.fv.data(),
                                (int)a.fv.size(), S(st));
   });
+  // forward-only inference of the flagship model over n resident images (runtime/persist_eval.py)
+  m.def("mnist_eval", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, u st) {
+    return hopsx_mnist_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), S(st));
+  });
+  m.def("mnist_eval_tile", []() { return hopsx_mnist_eval_tile(); });
   m.def("mnist_persist_reload_knobs", []() { hopsx_mnist_persist_reload_knobs(); });
   m.def("mnist_persist_occupancy", [](int dp) { return hopsx_mnist_persist_occupancy(dp); });
   m.def("pad_cin", [](u w, long R, int C, int cp, u out, u out16, u st) {

@@ -120,6 +120,10 @@ int hopsx_taxi_step2(const uint64_t* ptrs, int np, const long* iv, int ni, const
 int hopsx_mnist_persist(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf,
                         hipStream_t st);
 void hopsx_mnist_persist_geom(long* g);
+// ---- flagship MNIST CNN: forward-only inference of n resident uint8 images in one launch (mnist_eval.hip) ----
+// ptrs: master shadow xs ys(0 = logits only) logits loss hit totals part   iv: off[8] n max_workgroups   fv: xscale xshift
+int hopsx_mnist_eval(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, hipStream_t st);
+int hopsx_mnist_eval_tile();
 
 bool hopsx_conv_fwd_mfma_ok(const int* geom);
 bool hopsx_conv_fwd_pool_ok(const int* geom, int act, int pk);
