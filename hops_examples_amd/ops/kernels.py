@@ -475,15 +475,15 @@ def loss_fwd_bwd(kind: int, logits, target, grad_scale, loss_sum, correct, dlogi
 def optim_step(kind: int, param, grad, s1, s2, s3, shadow, hp, step_dev, zero_grad=True, arrive=None, rng=None,
                prefetch=None, hp_dev=None):
     """One fused update over flat buffers.  ``step_dev`` (f32[1]) counts completed steps and,
-    with ``arrive`` (int32[288], zero-initialised), is bumped in-kernel by the last workgroup,
-    together with the dropout RNG counter ``rng[1]`` when given.
+    with ``arrive`` (int32[kArriveWords], csrc/ops/common.h: 288 words, zero at rest), is bumped
+    in-kernel by the last workgroup, together with the dropout RNG counter ``rng[1]`` when given.
     ``prefetch`` = (pairs, cursor): pairs of (resident [nbatch, ...] tensor, static input buffer);
     the kernel copies batch (cursor+1) % nbatch into the buffers and advances the int64 cursor.
     ``hp_dev`` (f32[8] on the device): the kernel reads the hyper-parameters from it at run time
     instead of ``hp`` (so a replayed hipGraph sees learning-rate changes)."""
     n = param.numel()
     if step_dev is not None and arrive is None:
-        arrive = torch.zeros(9 * 32, device=param.device, dtype=torch.int32)  # optim_core.h kArriveWords
+        arrive = torch.zeros(9 * 32, device=param.device, dtype=torch.int32)  # common.h kArriveWords
     srcs, dsts, nbytes, cur, nb = [], [], [], 0, 0
     if prefetch is not None:
         pairs, cursor = prefetch

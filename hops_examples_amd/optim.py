@@ -17,7 +17,7 @@ import torch
 from .ops._C import OPTIM
 from .runtime.arena import ALIGN, ParamArena
 
-ARRIVE_WORDS = 9 * 32  # csrc/ops/optim_core.h kArriveWords
+ARRIVE_WORDS = 9 * 32  # csrc/ops/common.h kArriveWords
 
 
 def _arena_of(obj) -> ParamArena:
@@ -71,7 +71,7 @@ class FusedOptimizer:
         self.prefetch = None  # (pairs, cursor): fused next-batch copy of a resident dataset (TrainStep)
         dev = self.arena.device
         self.step_count = torch.zeros(1, device=dev, dtype=torch.float32)
-        # arrival counter of the in-kernel step bookkeeping: 8 per-XCD shards + top word (optim_core.h)
+        # arrival counter of the in-kernel step bookkeeping: 8 per-XCD shards + top word (common.h)
         self._arrive = torch.zeros(ARRIVE_WORDS, device=dev, dtype=torch.int32)
         # device RNG state advanced by the optimizer kernel's last workgroup (dropout masks)
         self.rng = None
@@ -164,6 +164,11 @@ class FusedOptimizer:
 
 
 class SGD(FusedOptimizer):
+    """``buf = momentum * buf + (1 - dampening) * g``; ``p -= lr * buf`` (nesterov: ``lr * (g + momentum * buf)``),
+    with L2 weight decay folded into ``g``.  The dampened form applies from the first step on (CPU and
+    kernel alike, from a zero buffer): ``torch.optim.SGD`` instead seeds the buffer with the undampened
+    first gradient, so with ``dampening != 0`` the first step differs from it."""
+
     kind, nstate = "sgd", 1
 
     def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0):
@@ -349,6 +354,80 @@ _BY_NAME = {"sgd": SGD, "adam": Adam, "adamw": AdamW, "adadelta": Adadelta, "rms
 
 def get(name: str, params, **kw) -> FusedOptimizer:
     return _BY_NAME[name.lower()](params, **kw)
+
+
+NSTATE = {"sgd": 1, "adam": 2, "adamw": 2, "adadelta": 2, "rmsprop": 3, "adagrad": 1, "ftrl": 2}
+
+
+def reference_step(kind, p, g, states, hp, t, dtype=torch.float64):
+    """One step of rule ``kind`` (name or kernel id) in plain ``dtype`` tensor arithmetic on the CPU:
+    what the optimizer kernel and every ``_cpu_step`` are checked against (fp64), and, evaluated in
+    fp32, the yardstick for how far an fp32 evaluation of the same formulas lies from fp64.
+
+    ``p``, ``g``: parameters and the raw (unscaled) gradient; ``states``: the rule's state streams in
+    the kernel's order (sgd: buf; adam(w): m, v; adadelta: E[g^2], E[dx^2]; rmsprop: square avg,
+    momentum buf, mean grad; adagrad: sum; ftrl: z, n); ``hp``: the kernel's 8-float vector (lr,
+    gscale, wd, a..e: the ``_hp()`` layouts), given as the fp32-rounded values the kernel receives;
+    ``t``: the number of this step (completed steps + 1), used by the Adam bias corrections, which
+    are computed in ``dtype`` from the rounded betas.  Nothing is modified; returns ``(p_new,
+    [state_new, ...])`` in ``dtype`` with the rule's NSTATE streams (a stream the configuration does
+    not use comes back as given)."""
+    kind = kind if isinstance(kind, str) else {v: k for k, v in OPTIM.items()}[int(kind)]
+    h = torch.tensor(([float(v) for v in hp] + [0.0] * 8)[:8], dtype=torch.float32)
+    on = [bool(v != 0) for v in h.tolist()]  # the branches the hyper-parameters select
+    lr, gscale, wd, a, b, c, d, e = h.to(dtype).unbind(0)
+    p = p.detach().to("cpu", dtype)
+    g = g.detach().to("cpu", dtype) * gscale
+    s = [x.detach().to("cpu", dtype) for x in list(states)[:NSTATE[kind]]]
+    if kind == "sgd":  # a momentum, b dampening, c nesterov
+        g = g + wd * p
+        if on[3]:
+            s[0] = a * s[0] + (1 - b) * g
+            g = g + a * s[0] if on[5] else s[0]
+        p = p - lr * g
+    elif kind in ("adam", "adamw"):  # a beta1, b beta2, c eps
+        if kind == "adam":
+            g = g + wd * p
+        else:
+            p = p - lr * wd * p
+        s[0] = a * s[0] + (1 - a) * g
+        s[1] = b * s[1] + (1 - b) * g * g
+        tt = torch.tensor(float(t), dtype=dtype)
+        bc1, bc2 = 1 - a ** tt, 1 - b ** tt
+        p = p - lr * (s[0] / bc1) / ((s[1] / bc2).sqrt() + c)
+    elif kind == "adadelta":  # a rho, b eps
+        g = g + wd * p
+        s[0] = a * s[0] + (1 - a) * g * g
+        delta = (s[1] + b).sqrt() / (s[0] + b).sqrt() * g
+        s[1] = a * s[1] + (1 - a) * delta * delta
+        p = p - lr * delta
+    elif kind == "rmsprop":  # a alpha, b eps, c momentum, d centered
+        g = g + wd * p
+        s[0] = a * s[0] + (1 - a) * g * g
+        if on[6]:
+            s[2] = a * s[2] + (1 - a) * g
+            avg = (s[0] - s[2] * s[2]).clamp_min(0).sqrt() + b
+        else:
+            avg = s[0].sqrt() + b
+        if on[5]:
+            s[1] = c * s[1] + g / avg
+            p = p - lr * s[1]
+        else:
+            p = p - lr * g / avg
+    elif kind == "adagrad":  # a eps
+        g = g + wd * p
+        s[0] = s[0] + g * g
+        p = p - lr * g / (s[0].sqrt() + a)
+    elif kind == "ftrl":  # a l1, b l2, c beta; s = z, n; lr_power = -0.5
+        nn_ = s[1] + g * g
+        sigma = (nn_.sqrt() - s[1].sqrt()) / lr
+        z = s[0] + g - sigma * p
+        s[0], s[1] = z, nn_
+        p = torch.where(z.abs() <= a, torch.zeros_like(z),
+                        -(z - torch.sign(z) * a) / ((c + nn_.sqrt()) / lr + 2 * b))
+    else:
+        raise ValueError(f"unknown optimizer kind {kind!r}")
+    return p, s
 
 
 def cosine_lr(base, step, total, warmup=0):
