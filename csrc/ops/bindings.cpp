@@ -272,6 +272,7 @@ HX_PYMOD(HOPSX_MODNAME) {
                          P<float>(dw), P<float>(db), P<void>(dh), P<float>(loss), P<int>(correct), P<float>(bias),
                          P<void>(lout), dp, P<unsigned long long>(drng), dsalt, S(st));
   });
+  m.def("mlp_head_lds", [](int C, int N1) { return hopsx_mlp_head_lds(C, N1); });
   m.def("mlp_head_debug", [](u p) { hopsx_mlp_head_debug(P<void>(p)); });
   // upload an instantiated hipGraph's executable to the device now (capture time) instead of at its
   // first launch (inside a timed loop / a latency-critical replay)

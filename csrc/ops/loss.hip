@@ -574,6 +574,13 @@ struct MlpLds {
   }
 };
 static size_t mlp_lds_bytes(int C, int N1) { return MlpLds(C, N1).total; }
+// dynamic LDS of one mlp_head_k workgroup; the launcher takes a shape only up to 64 KiB (the limit of a
+// launch without a raised hipFuncAttributeMaxDynamicSharedMemorySize).  0: C or N1 out of range
+extern "C" int hopsx_mlp_head_lds(int C, int N1) {
+  if (C < 1 || C > HEAD_CMAX || N1 < 16 || N1 % 16 || N1 > 256) return 0;
+  return (int)mlp_lds_bytes(C, N1);
+}
+constexpr int MLP_LDS_MAX = 65536;
 
 // loss + dlogits of one row per 16-lane group (C <= 16): max / sum / argmax by shuffles.  Kinds
 // 0/1 (softmax CE), 2/3/4 elementwise.  Adds this lane's loss / correct contributions.
@@ -599,11 +606,13 @@ __device__ inline void mlp_loss16(int kind, const float* slog, const void* targe
       const float lse = mx + __logf(se);
       const float p = ok ? __expf(z - lse) : 0.f;
       if (kind == 0) {
-        long lab = r < B ? ((const long*)target)[r] : -1;
-        if (r < B && c == 0 && !hx_guard((unsigned long)lab < (unsigned long)C)) lab = -1;
+        const long lab = r < B ? ((const long*)target)[r] : -1;
+        const bool inr = (unsigned long)lab < (unsigned long)C;
+        if (r < B && c == 0) (void)hx_guard(inr);
         if (ok) {
           sdl[r * C + c] = (p - (c == lab ? 1.f : 0.f)) * gs;
           if (c == lab) lacc += lse - z;
+          else if (c == 0 && !inr) lacc += lse;  // as row_thread: a label outside [0, C) contributes lse
           if (c == 0) cacc += (am == lab);
         }
       } else {
@@ -1011,7 +1020,7 @@ extern "C" int hopsx_mlp_head(const void* x, const void* w1, const float* b1, in
                               float* loss_sum, int* correct, void* logits_out, int logits_f32, float drop_p,
                               const unsigned long long* drop_rng, unsigned drop_salt, hipStream_t st) {
   if (hopsx_disabled("mlp_head") || B < 1 || B > HEAD_ROWS || N1 < 16 || N1 % 16 || N1 > 256 || K < 8 || K % 8 ||
-      !hopsx_head_ce_ok(C, N1) || !ws || !arrive || !logits_out ||
+      hopsx_mlp_head_lds(C, N1) < 1 || hopsx_mlp_head_lds(C, N1) > MLP_LDS_MAX || !ws || !arrive || !logits_out ||
       ((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)y | (uintptr_t)dh | (uintptr_t)ws) % 16)
     return -2;
   // K chunk per workgroup: 128 (4 MFMA k-steps).  At the flagship shape (K 10,816) the launch took

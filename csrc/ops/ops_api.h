@@ -59,6 +59,8 @@ int hopsx_head_ce(int kind, const void* logits, int logits_f32, const void* targ
 // the gradient of that input)
 // fused last hidden Dense + head (loss.hip mlp_head_k): y = act(x W1^T + b1) stored, then head_ce from
 // LDS; ws fp32 [B][N1] and arrive (kArriveWords) persistent, zero at rest.  -2: shape not supported
+// (the shape must fit 64 KiB of dynamic LDS: hopsx_mlp_head_lds(C, N1) bytes, 0 for a C / N1 out of range)
+int hopsx_mlp_head_lds(int C, int N1);
 int hopsx_mlp_head(const void* x, const void* w1, const float* b1, int act1, void* y, float* ws, unsigned* arrive,
                    int B, int K, int N1, int kind, const void* target, int C, float grad_scale, const void* w2,
                    const float* b2, float* dw2, float* db2, void* dh, float* loss_sum, int* correct,

@@ -1238,6 +1238,93 @@ def _cpu_loss(kind, logits, target, stats):
     return loss
 
 
+def _first_max(v):
+    """Index of the first maximal entry of every row, computed as the minimum index attaining the maximum."""
+    idx = torch.arange(v.shape[1]).expand_as(v)
+    return torch.where(v == v.max(1, keepdim=True).values, idx, v.shape[1]).min(1).values
+
+
+def loss_reference(kind: int, logits, target, grad_scale: float, dtype=torch.float64):
+    """Plain-tensor statement of what loss.hip computes from the operands as the kernels see them (host tensors):
+    returns ``(loss, correct, dlogits)`` with loss = grad_scale * sum of the row (kinds 0/1) or element (2/3/4)
+    losses, an int count, and dlogits [B, C] already scaled by grad_scale, evaluated in ``dtype`` (fp64: the
+    reference; fp32: the yardstick of the kernel tests).  A kind-0 label outside [0, C) reads no logit: its row
+    contributes its logsumexp, gets the plain softmax as gradient and is never counted correct."""
+    z = logits.to(dtype)
+    B, C = z.shape
+    gs = torch.tensor(grad_scale, dtype=torch.float32).to(dtype)
+    if kind in (0, 1):
+        mx = z.max(1, keepdim=True).values
+        lse = (mx + (z - mx).exp().sum(1, keepdim=True).log()).squeeze(1)
+        sm = (z - lse[:, None]).exp()
+        am = _first_max(z)
+        if kind == 0:
+            lab = target.long()
+            inr = (lab >= 0) & (lab < C)
+            safe = torch.where(inr, lab, torch.zeros_like(lab))
+            onehot = torch.zeros(B, C, dtype=dtype)
+            onehot[torch.arange(B), safe] = inr.to(dtype)
+            rows = lse - (z * onehot).sum(1)
+            dl = (sm - onehot) * gs
+            correct = int(((am == lab) & inr).sum())
+        else:
+            t = target.to(dtype)
+            ts = t.sum(1)
+            rows = ts * lse - (t * z).sum(1)
+            dl = (sm * ts[:, None] - t) * gs
+            correct = int((am == _first_max(target.float())).sum())
+        return rows.sum() * gs, correct, dl
+    y = target.to(dtype)
+    if kind == 2:
+        el = z.clamp(min=0) - z * y + torch.log1p((-z.abs()).exp())
+        g = torch.sigmoid(z) - y
+        correct = int(((logits.float() > 0) == (target.float() > 0.5)).sum())
+    elif kind == 3:
+        d = z - y
+        el, g, correct = d * d, 2 * d, 0
+    else:
+        f32 = torch.float32
+        eps = torch.tensor(1e-7, dtype=f32)
+        hi = torch.tensor(1.0, dtype=f32) - eps  # the fp32-rounded constants of the kernel, not the decimal ones
+        p = torch.minimum(torch.maximum(z, eps.to(dtype)), hi.to(dtype))
+        el = -(y * p.log() + (1 - y) * (1 - p).log())
+        flat = (logits.float() <= eps) | (logits.float() >= hi)
+        g = torch.where(flat, torch.zeros_like(p), (p - y) / (p * (1 - p)))
+        correct = int(((logits.float() > 0.5) == (target.float() > 0.5)).sum())
+    return el.sum() * gs, correct, g * gs
+
+
+def head_reference(kind: int, logits, target, grad_scale: float, h, w, mask=None, p: float = 0.0,
+                   dtype=torch.float64):
+    """The fused classifier head (loss.hip head_ce_k / mlp_head_k's tail) from the logits the loss sees and the
+    head's input ``h`` [B, KD] (after :func:`dropout_reference` when a Dropout feeds the head): the loss triple
+    of :func:`loss_reference` plus ``dw = dl^T h`` [C, KD], ``db = sum_r dl`` [C] (the increments the kernel adds)
+    and ``dh = dl W`` [B, KD], unrounded.  With ``mask`` (the Dropout's keep mask) ``dh`` is the gradient of the
+    Dropout's input: ``bf16(dl W) * mask / (1 - p)``, the kernel storing the bf16 rounding of it."""
+    loss_, correct, dl = loss_reference(kind, logits, target, grad_scale, dtype)
+    dh = dl @ w.to(dtype)
+    if mask is not None:
+        scale = (1.0 / (1.0 - torch.tensor(p, dtype=torch.float32))).to(dtype)
+        dh = dh.to(torch.bfloat16).to(dtype) * mask.to(dtype) * scale
+    return loss_, correct, dl, dl.t() @ h.to(dtype), dl.sum(0), dh
+
+
+def dense_reference(x, w, b=None, act=None, dtype=torch.float64):
+    """``act(x W^T + b)`` in ``dtype``, unrounded (the logits layer, and the Dense layer of mlp_head_k)."""
+    y = x.to(dtype) @ w.to(dtype).t()
+    if b is not None:
+        y = y + b.to(dtype)
+    return {None: lambda v: v, "none": lambda v: v, "relu": torch.relu, "sigmoid": torch.sigmoid,
+            "tanh": torch.tanh}[act](y)
+
+
+def dropout_reference(h, mask, p: float):
+    """The bf16 tensor a Dropout hands on: ``bf16(h * mask / (1 - p))``, the product formed in fp32 as
+    elementwise.hip dropout_k forms it (``mask`` from the project's generator: ``K.dropout(ones, ...) != 0``)."""
+    scale = 1.0 / (1.0 - torch.tensor(p, dtype=torch.float32))
+    return (h.float() * torch.where(mask, scale, torch.zeros(()))).to(torch.bfloat16)
+
+
 def loss_and_grad(logits, target, kind: str = "sparse_ce"):
     """Non-autograd fused loss for training loops that seed backward themselves:
     returns (mean loss [1], correct [1] int32, count, dlogits in the logits' dtype).

@@ -907,6 +907,15 @@ def mlp_head(x, w1, b1, act1, y, kind: int, logits, target, w2, b2, dw2, db2, gr
     return dh
 
 
+def mlp_head_lds(C: int, N1: int) -> int:
+    """Bytes of LDS one mlp_head_k workgroup needs for a C-way head on N1 hidden units (0: C or N1 out of its
+    range); mlp_head takes the shape only up to MLP_HEAD_LDS_MAX."""
+    return int(_C.ext().mlp_head_lds(int(C), int(N1)))
+
+
+MLP_HEAD_LDS_MAX = 65536
+
+
 def head_ce_ok(C: int, KD: int) -> bool:
     return bool(_C.ext().head_ce_ok(int(C), int(KD)))
 
