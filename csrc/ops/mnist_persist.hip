@@ -37,6 +37,14 @@
 // rows and advanced by nsteps at the end of each launch), so no memset precedes a launch.  Every
 // poll is bounded (wall clock) and also watches a sticky error word, so a fault drains the grid.
 // Payload buffers are double-buffered by step parity.
+// The fan-in C (169 partials -> each slice owner) is consumed progressively (gather_rows below,
+// HOPSX_PERSIST_PROG): each wave polls the flags of the producers whose rows its own lanes load and issues a
+// row's sc1 loads as soon as its own poll has shown that row's flag, whatever the order of arrival, so only the
+// last producers' rows are loaded after the last flag; the barrier moves behind the (unchanged, fixed-order)
+// sum.  Producers, payload, flags and epochs are those of the flag form.  (The same for the heads' fan-in A
+// measured SLOWER, 24.2 vs 23.6 us/step: the heads spin on A for ~10 us, and a poll issued behind a batch of
+// row loads returns only after them, so the last flag is seen later than by the bare poll;
+// profiles/r9_persist_progressive.txt.)
 // B towards the positions is the exception (the slowest hop in the flag form: 201 workgroups on one flag
 // line, a drain in the producer, a second round trip in the consumer): each head also stores dh as 64
 // 8-byte {bf16 pair, epoch} granules that are their own flag (G16 R2, "tagged granules" below), and the
@@ -170,7 +178,8 @@ struct Args {
   int head1w;          // 1: one wave computes the head from registers and publishes B (HOPSX_PERSIST_HEAD1W)
   // hand-off form, one word (one scalar register for the whole launch): bit 0: the positions read dh (B) from
   // tagged granules, not the flag form (HOPSX_PERSIST_TAGGED); bit 1: a flag poll loads the error word with
-  // its flags, one round trip (HOPSX_PERSIST_POLL1); bits 8..: heads whose tag opens the B wait's gate
+  // its flags, one round trip (HOPSX_PERSIST_POLL1); bit 3: the slice owners load a partial of C as soon as its
+  // flag is there (HOPSX_PERSIST_PROG bit 1); bits 8..: heads whose tag opens the B wait's gate
   // (HOPSX_PERSIST_GATE)
   int hand;
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
@@ -482,6 +491,46 @@ __device__ __forceinline__ bool sweep_tags(const unsigned long long* g, int tid,
   __syncthreads();
   const int f = *s_fail;
   return f == 0;
+}
+
+// ---- progressive fan-in (hand-off C): a row is loaded as soon as ITS flag is there ----
+// The flag form reads a fan-in payload only after the LAST producer's flag (poll, barrier, then every load), although
+// the producers finish up to a microsecond apart and almost every row has long been in memory by then.  Here every
+// wave polls the flags of exactly the producers whose rows its own lanes load — one flag per lane (`flag`, `mine`),
+// the error word in the same round trip — and the ballot of "flag == epoch" is the arrived set; bit `shift` + k of
+// it is this thread's row k.  Each thread then issues load(k) for every row of its `pend` mask that has arrived,
+// in any order of arrival (no in-order prefix: one late producer holds back only its own row), k static (the
+// pend-mask idiom of sweep_tags: the rows stay in registers), and polls again, with s_sleep, until no lane of the
+// wave has a row pending.  After the last flag only that flag's rows are still to load: one round trip.
+// Still row 1 of the "Valid forms" table: every load of handed-off bytes is an sc1 load issued by a wave after its
+// OWN poll has shown that producer's flag; no wave relies on another's poll.  Failure handling as sweep_tags: every
+// poll is bounded by `tmo` (recording `code`) and watches the sticky error word; a wave that gives up sets *s_fail.
+// No barrier in here: the caller reads *s_fail (uniform) behind the barrier that follows its reduce.
+template <int NK, class L>
+__device__ __forceinline__ void gather_rows(const unsigned* flag, bool mine, int shift, unsigned pend, unsigned epoch,
+                                            unsigned* err, unsigned code, int* s_fail, long long tmo, L load) {
+  const long long t0 = wall_clock64();
+  for (unsigned spins = 0;; ++spins) {
+    const unsigned e = flag_load(err);
+    const unsigned f = mine ? flag_load(flag) : 0u;
+    const unsigned long long here = __ballot(mine && f == epoch);
+    const unsigned now = pend & (unsigned)(here >> shift);
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+      if ((now >> k) & 1u) load(k);
+    pend &= ~now;
+    if (!__any(pend != 0u)) break;
+    bool bad = __builtin_amdgcn_readfirstlane(e) != 0u;
+    if (!bad && (spins & 15u) == 15u && wall_clock64() - t0 > tmo) {
+      if ((threadIdx.x & 63) == 0) atomicCAS(err, 0u, code);
+      bad = true;
+    }
+    if (bad) {
+      if ((threadIdx.x & 63) == 0) *s_fail = 1;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -934,10 +983,40 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     stamp(a, s, 6);
     // ---- slice owners: fixed-order reduce of 52 params over the 169 partials, Adadelta, publish D ----
     if (owner) {
+      const int e0 = p * SLICE;
+      constexpr int NKC = (NPOS + NRED - 1) / NRED;  // 9 partials per thread
+      static_assert(6 * NKC <= 64, "the flags of a wave's groups (64 threads span at most 6 groups of 13): one per lane");
+      if ((a.hand & 8) && !a.acquire) {
+        // progressive form (HOPSX_PERSIST_PROG bit 1): thread (g, j) loads its partials pp = g + 19 k as their
+        // flags arrive.  Wave w holds groups g0 .. g1 (at most 6, a group split over two waves is polled by
+        // both); its lane l polls the flag of group g0 + l / 9, partial k = l % 9: bit (g - g0) * 9 + k of the
+        // ballot is this thread's row k
+        const int j = tid % 13, g = tid / 13;
+        const bool act = g < NRED && e0 + 4 * j < NCONV;
+        const int g0 = (w * 64) / 13, g1 = (w * 64 + 63) / 13;
+        const int lg = g0 + lane / NKC, lp = lg + NRED * (lane % NKC);
+        const bool mine = lane < 6 * NKC && lg <= g1 && lg < NRED && lp < NPOS;
+        const auto R = rsrc(a.slabC + (long)par * NPOS * NCONV);
+        f32x4 v[NKC];
+#pragma unroll
+        for (int k = 0; k < NKC; ++k) v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        const unsigned pend = !act ? 0u : (g + NRED * (NKC - 1) < NPOS ? (1u << NKC) - 1u : (1u << (NKC - 1)) - 1u);
+        gather_rows<NKC>(a.flags + FL_C + lp, mine, act ? (g - g0) * NKC : 0, pend, ep, a.err, ecode(3, s), s_ok + 2,
+                         a.tmo, [&](int k) { v[k] = ld_sc1(R, ((g + NRED * k) * NCONV + e0 + 4 * j) * 4); });
+        stamp(a, s, 7);  // (the partials' load is inside the wait in this form)
+        if (g < NRED) {
+          f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int k = 0; k < NKC; ++k) acc += v[k];
+          *(f32x4*)(RED + g * SLICE + 4 * j) = acc;
+        }
+        __syncthreads();
+        const int f = s_ok[2];
+        if (f) return;
+      } else {
       if (!wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger, (a.hand & 2)))
         return;
       stamp(a, s, 7);
-      const int e0 = p * SLICE;
       if (tid < 13 * NRED) {
         const int j = tid % 13, g = tid / 13;
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -956,6 +1035,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         *(f32x4*)(RED + g * SLICE + 4 * j) = acc;
       }
       __syncthreads();
+      }
       const int e = e0 + tid;
       float gs = 0.f;
       if (tid < SLICE) {
@@ -1551,7 +1631,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.tmo0 = a.tmo;
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
-  static int kn_tagged, kn_gate, kn_poll1;
+  static int kn_tagged, kn_gate, kn_poll1, kn_prog;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1588,6 +1668,11 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     const long gt = hopsx_env_int("HOPSX_PERSIST_GATE", NHEAD / 2);
     kn_gate = (int)(gt >= 1 && gt <= NHEAD ? gt : NHEAD / 2);
     kn_poll1 = hopsx_env_int("HOPSX_PERSIST_POLL1", 1) != 0;
+    // progressive fan-in (gather_rows): bit 1 the slice owners' C partials (23.6 -> 23.0 us/step,
+    // profiles/r9_persist_progressive.txt); without it C is in the flag form (poll all, barrier, load), the only
+    // one HOPSX_PERSIST_POLLW_C still acts on.  Bit 0 was the heads' A rows: measured slower, not in the tree,
+    // ignored (so 3, the default, is 2 and 1 is 0)
+    kn_prog = (int)(hopsx_env_int("HOPSX_PERSIST_PROG", 3) & 2);
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1598,7 +1683,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.pollw_c = kn_c;
   a.pollw_d = kn_d;
   a.head1w = kn_head1w;
-  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_gate << 8);
+  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8);
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;
   a.inv_gb = 1.f / (float)(world * B);
   if (dp) {

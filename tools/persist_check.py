@@ -95,6 +95,12 @@ def timing(n, reps=5, loopback=0):
     # With the tagged B hand-off (HOPSX_PERSIST_TAGGED=1, the default) the positions sweep the dh granules
     # straight into LDS inside the wait, so the dh load is part of the "wait B" row and the next row is the fc1
     # wgrad/dgrad + pool bwd alone; with HOPSX_PERSIST_TAGGED=0 (flag form) the rows mean what they say
+    # With the progressive fan-in of C (HOPSX_PERSIST_PROG bit 1, the default; same stamp indices) the owners load
+    # a partial inside the wait, as soon as its flag is there: "owner: wait C" and "last C publish -> owners' C
+    # ready" end when the owner holds its 169 partials in registers, and "owner: slice reduce ..." is the sum
+    # onwards, without the 35 KB load.  So compare the SUM of the two owner rows between the forms, not each row;
+    # with HOPSX_PERSIST_PROG=0 they mean what they say.  (A, "last A publish -> A ready" / "head compute", is
+    # in the flag form either way)
 
     rows = [("conv fwd (input, conv1, conv2 MFMA, pool, dropout)", pos, 0, 1), ("fc1 partial + publish A", pos, 1, 2),
             ("wait B (heads)", pos, 2, 3), ("dh load + fc1 wgrad/dgrad + pool bwd", pos, 3, 4),
