@@ -653,73 +653,105 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       const int ci = tid & 31, bg = tid >> 5;
       const float k0 = CW1[ci * 4 + 0], k1 = CW1[ci * 4 + 1], k2 = CW1[ci * 4 + 2], k3 = CW1[ci * 4 + 3];
       const float bias = CB1[ci];
+      f32x4 xq[4][4];  // the 4x4 patches of this thread's 4 images, all in flight before the first use
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xq[u][c] = *(const f32x4*)(XIN + (bg * 4 + u) * 16 + 4 * c);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int b = bg * 4 + u;
-        const float* xi = XIN + b * 16;
+        const f32x4* xi = xq[u];
 #pragma unroll
         for (int py = 0; py < 3; ++py)
 #pragma unroll
           for (int px = 0; px < 3; ++px) {
             float v = bias;
-            v = fmaf(xi[py * 4 + px], k0, v);
-            v = fmaf(xi[py * 4 + px + 1], k1, v);
-            v = fmaf(xi[(py + 1) * 4 + px], k2, v);
-            v = fmaf(xi[(py + 1) * 4 + px + 1], k3, v);
+            v = fmaf(xi[py][px], k0, v);
+            v = fmaf(xi[py][px + 1], k1, v);
+            v = fmaf(xi[py + 1][px], k2, v);
+            v = fmaf(xi[py + 1][px + 1], k3, v);
             C1[(b * 9 + py * 3 + px) * C1S + ci] = f2bf(fmaxf(v, 0.f));
           }
       }
     }
     __syncthreads();
     // ---- conv2 (MFMA, rows (b, q) = b*4 + q, k = tap*32 + ci) + bias + relu + max-pool + dropout ----
+    // (one wave per SIMD: an LDS read that is waited for at once exposes its whole latency, so every phase below
+    // issues its LDS reads in batches ahead of their uses — the fragments of MFMA step kk + 1 while step kk's MFMAs
+    // issue, two register sets — and sched_barrier keeps the compiler from sinking them back next to the uses)
     {
       f32x4 acc[2][4];
 #pragma unroll
       for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[ii][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      // the epilogue's operands (4 biases, 8 keep bytes), read ahead of the MFMA loop
+      float bias[4];
+      unsigned char keep[2][4];
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
+      for (int j = 0; j < 4; ++j) {
+        bias[j] = CB2[j * 16 + fr];
+#pragma unroll
+        for (int ii = 0; ii < 2; ++ii) keep[ii][j] = KEEP[(4 * (2 * w + ii) + fq) * C2 + j * 16 + fr];
+      }
+      bf16x8 af[2][2], bfr[2][4];
+      auto frag = [&](int kk, int st) {
         const int di = kk >> 1, dj = kk & 1;
-        bf16x8 af[2];
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii) {
           const int b = 4 * (2 * w + ii) + (fr >> 2), q = fr & 3;
           const int pos = ((q >> 1) + di) * 3 + (q & 1) + dj;
-          af[ii] = lds8(C1 + (b * 9 + pos) * C1S + fq * 8);
+          af[st][ii] = lds8(C1 + (b * 9 + pos) * C1S + fq * 8);
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bf16x8 bfr = lds8(W2 + (j * 16 + fr) * W2S + kk * 32 + fq * 8);
+        for (int j = 0; j < 4; ++j) bfr[st][j] = lds8(W2 + (j * 16 + fr) * W2S + kk * 32 + fq * 8);
+      };
+      frag(0, 0);
 #pragma unroll
-          for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mfma(af[ii], bfr, acc[ii][j]);
-        }
+      for (int kk = 0; kk < 4; ++kk) {
+        if (kk + 1 < 4) frag(kk + 1, (kk + 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mfma(af[kk & 1][ii], bfr[kk & 1][j], acc[ii][j]);
       }
+      bf16_raw pv[2][4];
+      unsigned char av[2][4];
 #pragma unroll
       for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int b = 4 * (2 * w + ii) + fq, co = j * 16 + fr;
-          const float bias = CB2[co];
           float best = -INFINITY;
           int bi = 0;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = bf2f(f2bf(fmaxf(acc[ii][j][r] + bias, 0.f)));  // bf16 conv output, as unfused
+            const float v = bf2f(f2bf(fmaxf(acc[ii][j][r] + bias[j], 0.f)));  // bf16 conv output, as unfused
             if (v > best) {
               best = v;
               bi = r;
             }
           }
           if (!(best > 0.f)) bi = 0xFF;
-          if (KEEP[b * C2 + co]) {
+          if (keep[ii][j]) {
             best *= inv;
           } else {
             best = 0.f;
             bi = 0xFF;
           }
-          POOL[b * PLS + co] = f2bf(best);
-          AM[b * C2 + co] = (unsigned char)bi;
+          pv[ii][j] = f2bf(best);
+          av[ii][j] = (unsigned char)bi;
+        }
+      // (the stores after all the math: a store between two reads would be waited out with them)
+#pragma unroll
+      for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int b = 4 * (2 * w + ii) + fq, co = j * 16 + fr;
+          POOL[b * PLS + co] = pv[ii][j];
+          AM[b * C2 + co] = av[ii][j];
         }
     }
     __syncthreads();
@@ -731,18 +763,21 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      bf16x8 af[2][2], bfr[2][2];  // both k steps' fragments in flight before the first MFMA
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 af[2], bfr[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) af[i] = lds8(POOL + (i * 16 + fr) * PLS + kk * 32 + fq * 8);
+        for (int i = 0; i < 2; ++i) af[kk][i] = lds8(POOL + (i * 16 + fr) * PLS + kk * 32 + fq * 8);
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) bfr[jj] = lds8(W1 + ((2 * w + jj) * 16 + fr) * W1S + kk * 32 + fq * 8);
+        for (int jj = 0; jj < 2; ++jj) bfr[kk][jj] = lds8(W1 + ((2 * w + jj) * 16 + fr) * W1S + kk * 32 + fq * 8);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma(af[i], bfr[jj], acc[i][jj]);
-      }
+          for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma(af[kk][i], bfr[kk][jj], acc[i][jj]);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -753,11 +788,12 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     __syncthreads();
     {  // publish A
       const auto R = rsrc(a.slabA + ((long)par * NPOS + p) * (B * HID));
+      f32x4 v[4];  // every LDS read of the staging tile first, then the write-through stores
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int idx = tid + 256 * k;
-        st_sc1(R, idx * 16, *(const f32x4*)(STG + idx * 4));
-      }
+      for (int k = 0; k < 4; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) st_sc1(R, (tid + 256 * k) * 16, v[k]);
       drain();
       __syncthreads();
       if (tid == 0) flag_store(a.flags + FL_A + p, ep);
@@ -820,34 +856,33 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     }
     __syncthreads();
     }
-    // ---- fc1 weight gradient (lane-owned layout) and input gradient ----
+    // ---- fc1 input gradient ----
     f32x4 gw[2][4], dp[2];
+    unsigned char amv[2][4];  // the pool backward's argmax bytes, read with the fragments
     {
-      // data parallel: the weight gradient sums every replica's images in rank order at the end of
-      // the step (below); here only the input gradient
-      if constexpr (!DP) {
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {  // A = dh^T (row n, k = b)
-        const int n0 = (2 * w + ii) * 16 + 4 * tp;
-        const bf16x8 af = lds_tr(DH + (8 * fq + tq) * DHS + n0, DH + (8 * fq + tq + 4) * DHS + n0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // B = pooled (col co, k = b)
-          const int c0 = j * 16 + 4 * tp;
-          const bf16x8 bfr = lds_tr(POOL + (8 * fq + tq) * PLS + c0, POOL + (8 * fq + tq + 4) * PLS + c0);
-          gw[ii][j] = mfma(af, bfr, (f32x4){0.f, 0.f, 0.f, 0.f});
-        }
-      }
-      }
-      dp[0] = dp[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      // every fragment and the 8 argmax bytes in flight before the first MFMA
+      // (the weight gradient, which only the Adadelta at the end of the step needs, is computed behind the
+      // first part of the C publish below: everything up to that publish is on the step's critical path)
+      bf16x8 da[4][2], db4[4];
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {  // A = dh (row b, k = n), B = W1^T (col co, k = n)
         const int k1 = kk * 32 + 8 * fq + tq;
-        const bf16x8 bfr = lds_tr(W1 + k1 * W1S + w * 16 + 4 * tp, W1 + (k1 + 4) * W1S + w * 16 + 4 * tp);
+        db4[kk] = lds_tr(W1 + k1 * W1S + w * 16 + 4 * tp, W1 + (k1 + 4) * W1S + w * 16 + 4 * tp);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dp[i] = mfma(lds8(DH + (i * 16 + fr) * DHS + kk * 32 + fq * 8), bfr, dp[i]);
+        for (int i = 0; i < 2; ++i) da[kk][i] = lds8(DH + (i * 16 + fr) * DHS + kk * 32 + fq * 8);
       }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) amv[i][r] = AM[(i * 16 + fq * 4 + r) * C2 + w * 16 + fr];
+      __builtin_amdgcn_sched_barrier(0);
+      dp[0] = dp[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) dp[i] = mfma(da[kk][i], db4[kk], dp[i]);
     }
-    // (no barrier: the phases up to the C publish write neither DH, POOL nor W1)
+    // (no barrier: the phases up to the fc1 Adadelta write neither DH, POOL nor W1)
     // ---- dropout / max-pool / relu backward -> dconv2[(b,q)][co]; conv2 bias gradient ----
     {
       const int co = w * 16 + fr;
@@ -857,7 +892,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int b = i * 16 + fq * 4 + r;
-          const int am = AM[b * C2 + co];
+          const int am = amv[i][r];
           const bf16_raw gb = am != 0xFF ? f2bf(dp[i][r] * inv) : (bf16_raw)0;
           db += bf2f(gb);
           // the image's 4 window taps are adjacent columns of row co: one 8-byte store
@@ -868,70 +903,122 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       db += __shfl_xor(db, 32, 64);
       if (fq == 0) STG[OFF_B2 + co] = db;
     }
-    __syncthreads();
-    stamp(a, s, 4);
     // ---- conv2 weight gradient: dW2[co][(t,ci)] = sum_(b,q) dconv2[(b,q)][co] im2col[(b,q)][(t,ci)] ----
     {
       f32x4 acc[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const int k1 = kk * 32 + 8 * fq + tq, b1 = k1 >> 2, q1 = k1 & 3;  // k1 + 4 = image b1 + 1, same q
-        const bf16x8 af = lds8(DC2 + (w * 16 + fr) * DCS + kk * 32 + fq * 8);
+      // k = kk*32 + 8*fq + tq is image b1 = kk*8 + 2*fq, window tap q1 = tq (k + 4 = image b1 + 1, same q): a
+      // step's 8 im2col fragments sit at compile-time offsets from one base address per lane
+      const bf16_raw* cb = C1 + (2 * fq * 9 + (tq >> 1) * 3 + (tq & 1)) * C1S + 4 * tp;
+      bf16x8 af[2], bfr[2][8];
+      auto cfrag = [&](int kk, int st) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const int t = j >> 1, ci0 = (j & 1) * 16 + 4 * tp;
-          const int pos = ((q1 >> 1) + (t >> 1)) * 3 + (q1 & 1) + (t & 1);
-          const bf16x8 bfr = lds_tr(C1 + (b1 * 9 + pos) * C1S + ci0, C1 + ((b1 + 1) * 9 + pos) * C1S + ci0);
-          acc[j] = mfma(af, bfr, acc[j]);
+          const int t = j >> 1;
+          const bf16_raw* q = cb + (kk * 8 * 9 + (t >> 1) * 3 + (t & 1)) * C1S + (j & 1) * 16;
+          bfr[st][j] = lds_tr(q, q + 9 * C1S);
         }
+      };
+      auto afrag = [&](int kk, int st) { af[st] = lds8(DC2 + (w * 16 + fr) * DCS + kk * 32 + fq * 8); };
+      cfrag(0, 0);  // (C1 is this step's conv1 output: readable ahead of the barrier that publishes DC2)
+      __syncthreads();
+      stamp(a, s, 4);
+      afrag(0, 0);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        if (kk + 1 < 4) {
+          afrag(kk + 1, (kk + 1) & 1);
+          cfrag(kk + 1, (kk + 1) & 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = mfma(af[kk & 1], bfr[kk & 1][j], acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) STG[(w * 16 + fq * 4 + r) * 128 + j * 16 + fr] = acc[j][r];
     }
-    __syncthreads();
-    {  // publish C, part 1: the conv2 weight gradient (8192 floats) now; its write-through stores drain
-       // while the conv2 input gradient and the conv1 gradient below are computed
-      const auto R = rsrc(a.slabC + ((long)par * NPOS + p) * NCONV);
-#pragma unroll
-      for (int k = 0; k < OFF_B2 / 4 / 256; ++k) {
-        const int idx = tid + 256 * k;
-        st_sc1(R, idx * 16, *(const f32x4*)(STG + idx * 4));
-      }
-    }
     // ---- conv2 input gradient -> col2im -> relu' -> conv1 weight / bias gradient ----
     {
-      const int mh = w >> 1, h = w & 1;
+      const int mh = w >> 1, h = w & 1, ci = h * 16 + fr;
+      // both k steps' fragments are read ahead of the barrier below (DC2 and W2 are
+      // stable here), so they arrive while the publish's staging reads and stores issue
+      bf16x8 af[2][4], bfr[2][4];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int k1 = kk * 32 + 8 * fq + tq;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int m0 = (mh * 4 + i) * 16 + 4 * tp;
+          af[kk][i] = lds_tr(DC2 + k1 * DCS + m0, DC2 + (k1 + 4) * DCS + m0);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int c0 = (2 * t + h) * 16 + 4 * tp;
+          bfr[kk][t] = lds_tr(W2 + k1 * W2S + c0, W2 + (k1 + 4) * W2S + c0);
+        }
+      }
+      __syncthreads();
+      {  // publish C, part 1: the conv2 weight gradient (8192 floats) now; its write-through stores drain
+         // while the conv2 input gradient and the conv1 gradient below are computed
+        const auto R = rsrc(a.slabC + ((long)par * NPOS + p) * NCONV);
+        constexpr int NK = OFF_B2 / 4 / 256;
+        f32x4 v[NK];  // every LDS read of the staging tile first, then the write-through stores
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) st_sc1(R, (tid + 256 * k) * 16, v[k]);
+      }
       f32x4 acc[4][4];  // [M tile mh*4+i][tap t (N tile 2t+h)]
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[i][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 af[4];
-        const int k1 = kk * 32 + 8 * fq + tq;
+      for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m0 = (mh * 4 + i) * 16 + 4 * tp;
-          af[i] = lds_tr(DC2 + k1 * DCS + m0, DC2 + (k1 + 4) * DCS + m0);
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][t] = mfma(af[kk][i], bfr[kk][t], acc[i][t]);
+      // relu' of conv1: the 36 conv1 outputs of this lane's (b, ci), all in flight while the MFMAs run
+      bf16_raw c1v[4][9];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int pos = 0; pos < 9; ++pos) c1v[i][pos] = C1[((4 * (mh * 4 + i) + fq) * 9 + pos) * C1S + ci];
+      // ---- fc1 weight gradient (lane-owned layout), off the critical path: the C publish is draining ----
+      // data parallel: the weight gradient sums every replica's images in rank order at the end of
+      // the step (below)
+      if constexpr (!DP) {
+        bf16x8 wa[2], wb[4];
+#pragma unroll
+        for (int ii = 0; ii < 2; ++ii) {  // A = dh^T (row n, k = b)
+          const int n0 = (2 * w + ii) * 16 + 4 * tp;
+          wa[ii] = lds_tr(DH + (8 * fq + tq) * DHS + n0, DH + (8 * fq + tq + 4) * DHS + n0);
         }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int c0 = (2 * t + h) * 16 + 4 * tp;
-          const bf16x8 bfr = lds_tr(W2 + k1 * W2S + c0, W2 + (k1 + 4) * W2S + c0);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[i][t] = mfma(af[i], bfr, acc[i][t]);
+        for (int j = 0; j < 4; ++j) {  // B = pooled (col co, k = b)
+          const int c0 = j * 16 + 4 * tp;
+          wb[j] = lds_tr(POOL + (8 * fq + tq) * PLS + c0, POOL + (8 * fq + tq + 4) * PLS + c0);
         }
+#pragma unroll
+        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gw[ii][j] = mfma(wa[ii], wb[j], (f32x4){0.f, 0.f, 0.f, 0.f});
       }
-      const int ci = h * 16 + fr;
       float gk[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+      f32x4 xq[2][4];  // image b's 4x4 input patch, read one image ahead of its use
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xq[0][c] = *(const f32x4*)(XIN + (4 * (mh * 4) + fq) * 16 + 4 * c);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int b = 4 * (mh * 4 + i) + fq;
+        if (i + 1 < 4) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) xq[(i + 1) & 1][c] = *(const f32x4*)(XIN + (4 * (mh * 4 + i + 1) + fq) * 16 + 4 * c);
+        }
         float d[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) d[k] = 0.f;
@@ -939,17 +1026,17 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int q = 0; q < 4; ++q) d[((q >> 1) + (t >> 1)) * 3 + (q & 1) + (t & 1)] += acc[i][t][q];
-        const float* xi = XIN + b * 16;
+        const f32x4* xi = xq[i & 1];
 #pragma unroll
         for (int py = 0; py < 3; ++py)
 #pragma unroll
           for (int px = 0; px < 3; ++px) {
             const int pos = py * 3 + px;
-            const float dd = (short)C1[(b * 9 + pos) * C1S + ci] > 0 ? d[pos] : 0.f;  // relu' of conv1
-            gk[0] = fmaf(dd, xi[py * 4 + px], gk[0]);
-            gk[1] = fmaf(dd, xi[py * 4 + px + 1], gk[1]);
-            gk[2] = fmaf(dd, xi[(py + 1) * 4 + px], gk[2]);
-            gk[3] = fmaf(dd, xi[(py + 1) * 4 + px + 1], gk[3]);
+            const float dd = (short)c1v[i][pos] > 0 ? d[pos] : 0.f;  // relu' of conv1
+            gk[0] = fmaf(dd, xi[py][px], gk[0]);
+            gk[1] = fmaf(dd, xi[py][px + 1], gk[1]);
+            gk[2] = fmaf(dd, xi[py + 1][px], gk[2]);
+            gk[3] = fmaf(dd, xi[py + 1][px + 1], gk[3]);
             gk[4] += dd;
           }
       }
@@ -1004,6 +1091,12 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         gather_rows<NKC>(a.flags + FL_C + lp, mine, act ? (g - g0) * NKC : 0, pend, ep, a.err, ecode(3, s), s_ok + 2,
                          a.tmo, [&](int k) { v[k] = ld_sc1(R, ((g + NRED * k) * NCONV + e0 + 4 * j) * 4); });
         stamp(a, s, 7);  // (the partials' load is inside the wait in this form)
+        // every lane names its partial registers here, so the compiler waits for the loads on every path into the
+        // sum (the sum's lanes wait here anyway).  Left to the conditional sum, its bookkeeping keeps them pending
+        // along the path around it and waits vmcnt(0) where those registers are next written: that landed behind
+        // the D flag store, and wave 0 waited out the store's round trip (0.5 us) before its fc1 Adadelta
+#pragma unroll
+        for (int k = 0; k < NKC; ++k) asm volatile("" ::"v"(v[k]));
         if (g < NRED) {
           f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
