@@ -73,6 +73,7 @@ extern "C" int hopsx_dbg_read_rowreduce(unsigned* out);
 extern "C" int hopsx_dbg_read_wgrad_glds(unsigned* out);
 extern "C" int hopsx_dbg_read_embedding(unsigned* out);
 extern "C" int hopsx_dbg_read_mnist_eval(unsigned* out);
+extern "C" int hopsx_dbg_read_taxi_eval(unsigned* out);
 
 // the debug build (-DHOPSX_DEBUG=1) is the module _hopsx_ops_dbg (same sources, hx_check compiled in)
 #ifndef HOPSX_MODNAME
@@ -163,6 +164,7 @@ HX_PYMOD(HOPSX_MODNAME) {
     {"wgrad_glds", hopsx_dbg_read_wgrad_glds},
     {"embedding", hopsx_dbg_read_embedding},
     {"mnist_eval", hopsx_dbg_read_mnist_eval},
+    {"taxi_eval", hopsx_dbg_read_taxi_eval},
     };
     std::vector<std::tuple<std::string, unsigned, unsigned, unsigned, unsigned>> out;
     for (const auto& t : tus) {
@@ -218,6 +220,11 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_mnist_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), S(st));
   });
   m.def("mnist_eval_tile", []() { return hopsx_mnist_eval_tile(); });
+  // one-launch sliced evaluation of the taxi wide & deep model (runtime/taxi_eval.py)
+  m.def("taxi_eval", [](std::vector<uint64_t> p, std::vector<long> iv, u st) {
+    return hopsx_taxi_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), S(st));
+  });
+  m.def("taxi_eval_bins", []() { return hopsx_taxi_eval_bins(); });
   m.def("mnist_persist_reload_knobs", []() { hopsx_mnist_persist_reload_knobs(); });
   m.def("mnist_persist_occupancy", [](int dp) { return hopsx_mnist_persist_occupancy(dp); });
   m.def("pad_cin", [](u w, long R, int C, int cp, u out, u out16, u st) {

@@ -126,6 +126,11 @@ void hopsx_mnist_persist_geom(long* g);
 // ptrs: master shadow xs ys(0 = logits only) logits loss hit totals part   iv: off[8] n max_workgroups   fv: xscale xshift
 int hopsx_mnist_eval(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, hipStream_t st);
 int hopsx_mnist_eval_tile();
+// ---- Chicago-taxi wide & deep: forward + sliced metric accumulators of n resident rows in one launch (taxi_eval.hip) ----
+// ptrs: master shadow dense cat label(0 = logits / probabilities only) logit prob loss hit acc
+// iv:   woff[5] boff[5] wide_off rows n slice_col(-1 = none) max_workgroups
+int hopsx_taxi_eval(const uint64_t* ptrs, int np, const long* iv, int ni, hipStream_t st);
+int hopsx_taxi_eval_bins();
 
 bool hopsx_conv_fwd_mfma_ok(const int* geom);
 bool hopsx_conv_fwd_pool_ok(const int* geom, int act, int pk);

@@ -28,4 +28,17 @@ assert all(v == "success" for v in state.values()), getattr(dag, "errors", {})
 # %%
 for stage in ("transform/transform_stats.json", "trainer/metrics.json", "evaluator/metrics.json",
               "pusher/result.json"):
-    print(stage, json.loads((root / stage).read_text()))
+    print(stage, {k: v for k, v in json.loads((root / stage).read_text()).items() if k != "slices"})
+
+# %% [markdown]
+# ## Model analysis
+# The Evaluator's metrics per `trip_start_hour` (TFMA's slicing of the TFX taxi example): one launch of the
+# sliced evaluator over the whole eval split on the GPU (`runtime/taxi_eval.py`).
+# %%
+ev = json.loads((root / "evaluator" / "metrics.json").read_text())
+print(f"path {ev['path']}  rows {ev['eval_rows']}  accuracy {ev['accuracy']:.4f}  auc {ev['auc']:.4f}  "
+      f"auc_bucketed {ev['auc_bucketed']:.4f}")
+print("hour   rows  positives  accuracy  log_loss  calibration  auc_bucketed")
+for hour, s in ev["slices"]["trip_start_hour"].items():
+    print(f"{int(hour):4d} {s['count']:6d} {s['positives']:10d} {s['accuracy']:9.4f} {s['log_loss']:9.4f} "
+          f"{s['calibration']:12.4f} {s['auc_bucketed']:13.4f}")

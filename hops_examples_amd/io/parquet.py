@@ -328,7 +328,9 @@ class ParquetDeviceReader:
                 with torch.cuda.stream(st.stream):
                     dev[:nb].copy_(host[:nb], non_blocking=True)  # one hipMemcpyAsync per row group
                     srcs = [dev[o:o + n].view(_torch_dtype(dt)) for (dt, n), o in zip(cols, offs)]
-                    K.cols_to_f32(srcs, out[r0:r0 + m])  # convert + interleave: one launch per row group
+                    # convert + interleave: one launch per row group and 16 columns (the kernel's column limit)
+                    for c0 in range(0, len(srcs), 16):
+                        K.cols_to_f32(srcs[c0:c0 + 16], out[r0:r0 + m, c0:])
                     e = torch.cuda.Event()
                     e.record(st.stream)
                 slot[2] = e

@@ -12,7 +12,9 @@ Transform          analyze on train, apply to both splits (:mod:`.transform`; tr
                    ``transform/transform_fn.json`` + ``transformed/{train,eval}.parquet``
 Trainer            wide&deep trainer (``models.widedeep``: the whole step in one kernel) fed by the
                    transformed Parquet streamed into HBM (``io.parquet``) -> ``trainer/model.pt``
-Evaluator          accuracy / AUC / log-loss on the eval split; blesses the model above a threshold
+Evaluator          accuracy / AUC / log-loss on the eval split, overall and per slice of a feature (TFMA's
+                   model analysis; ``runtime.taxi_eval``: the whole split in one launch on the GPU);
+                   blesses the model above a threshold
 Pusher             exports a blessed model + its transform_fn to the model registry (``model.export``)
 =================  ==========================================================================
 
@@ -126,7 +128,11 @@ def _load_transformed(root: Path, split: str, device):
     return dense, cat, label
 
 
-def trainer(root, steps: int = 2000, batch: int = 40, device=None) -> dict:
+def trainer(root, steps: int = 2000, batch: int = 40, device=None, eval_every: int = 0) -> dict:
+    """``eval_every`` = k > 0 (the fused step with the one-launch evaluator; TFX's ``train_and_evaluate``):
+    the resident steps run in pieces of k, each followed — with no sync — by an evaluation of the eval
+    split, recorded in ``metrics.json["eval_curve"]``.  The evaluator only reads: the final weights are
+    those of ``eval_every=0``."""
     import torch
 
     from ..models.widedeep import FusedWideDeepStep, TaxiWideDeep, make_optimizer
@@ -148,7 +154,25 @@ def trainer(root, steps: int = 2000, batch: int = 40, device=None) -> dict:
     ys = label[:nb * batch].view(nb, batch, 1).contiguous()
     fused = FusedWideDeepStep(model, opt) if dev.type == "cuda" else None
     t0 = time.perf_counter()
-    if fused is not None and fused.ok(batch):
+    evals = []
+    if fused is not None and fused.ok(batch) and eval_every > 0:
+        from ..runtime.taxi_eval import TaxiEvaluator, metrics
+
+        if not TaxiEvaluator.supported(model):
+            raise ValueError("eval_every needs the one-launch evaluator (runtime.taxi_eval.TaxiEvaluator.supported)")
+        e_dense, e_cat, e_label = _load_transformed(root, "eval", dev)
+        ev = TaxiEvaluator(model)
+        t0 = time.perf_counter()
+        done = 0
+        while done < steps:
+            k = min(int(eval_every), steps - done)
+            r = fused.run_resident(xs, ys, k)  # (the device cursor continues across calls)
+            done += k
+            evals.append((done, ev.run(e_dense, e_cat, e_label)))  # stream order: reads what the launch wrote back
+        path = "fused"
+    elif eval_every > 0:
+        raise ValueError("eval_every needs the fused training step (one GPU, the default taxi shape)")
+    elif fused is not None and fused.ok(batch):
         r = fused.run_resident(xs, ys, steps)
         path = "fused"
     else:
@@ -166,6 +190,9 @@ def trainer(root, steps: int = 2000, batch: int = 40, device=None) -> dict:
     res = {"model": str(p), "steps": steps, "batch": batch, "train_rows": int(dense.shape[0]), "step": path,
            "steps_per_sec": round(steps / el, 1), "final_loss": round(float(r["loss"].reshape(-1)[0]), 4),
            "device": str(dev)}
+    if eval_every > 0:
+        res["eval_curve"] = [{"step": s, **{k: metrics(e)["overall"][k] for k in ("log_loss", "accuracy", "auc_bucketed")}}
+                             for s, e in evals]
     _write_json(root / "trainer" / "metrics.json", res)
     return res
 
@@ -178,10 +205,15 @@ def _auc(score: np.ndarray, y: np.ndarray) -> float:
     return float((ranks[pos].sum() - pos.sum() * (pos.sum() + 1) / 2) / (pos.sum() * neg.sum()))
 
 
-def evaluator(root, threshold: float = 0.6, device=None) -> dict:
+def evaluator(root, threshold: float = 0.6, device=None, slice_by=("trip_start_hour",)) -> dict:
+    """Global accuracy / rank AUC / log-loss from the per-row probabilities, plus TFMA-style metrics per slice
+    of each ``slice_by`` feature (``"slices": {feature: {slice value: metrics}}``) and the bucketed AUC.
+    ``"path"``: "fused" — probabilities and sliced metrics from ``runtime.taxi_eval.TaxiEvaluator``, one
+    launch per feature — or "layerwise": the chunked forward, the slices from ``metrics_from_rows``."""
     import torch
 
-    from ..models.widedeep import TaxiWideDeep
+    from ..models.widedeep import TaxiWideDeep, wide_cardinalities
+    from ..runtime import taxi_eval as TE
     from ..runtime.arena import ParamArena
 
     root = Path(root)
@@ -192,16 +224,38 @@ def evaluator(root, threshold: float = 0.6, device=None) -> dict:
     model.load_state_dict(torch.load(root / "trainer" / "model.pt", map_location="cpu", weights_only=True))
     model.to(dev)
     ParamArena.from_module(model, dev)
-    with torch.no_grad():
-        logits = torch.cat([model(dense[i:i + 4096], cat[i:i + 4096]).float()
-                            for i in range(0, dense.shape[0], 4096)])
-    p = torch.sigmoid(logits).cpu().numpy()[:, 0]
+    feats = [slice_by] if isinstance(slice_by, (str, int)) else list(slice_by or ())
+    feats = [TE.WIDE_FEATURE_KEYS[TE.slice_column(f)] for f in feats]
     y = label.cpu().numpy()[:, 0]
+    slices = {}
+    if dev.type == "cuda" and TE.TaxiEvaluator.supported(model):
+        path = "fused"
+        ev = TE.TaxiEvaluator(model)
+        for f in feats or [None]:
+            r = ev.run(dense, cat, label, slice_by=f)
+            m = TE.metrics(r)
+            if f is not None:
+                slices[f] = {str(v): s for v, s in enumerate(m["slices"])}
+        p = r.prob.cpu().numpy()
+    else:
+        path = "layerwise"
+        with torch.no_grad():
+            logits = torch.cat([model(dense[i:i + 4096], cat[i:i + 4096]).float()
+                                for i in range(0, dense.shape[0], 4096)])
+        p = torch.sigmoid(logits).cpu().numpy()[:, 0]
+        loss = TE.bce_with_logits(logits.cpu().numpy()[:, 0], y)
+        for f in feats or [None]:
+            col = TE.slice_column(f)
+            m = TE.metrics_from_rows(p, loss, y, TE.slice_ids_of(cat, col) if col >= 0 else None,
+                                     wide_cardinalities()[col] if col >= 0 else 0)
+            if f is not None:
+                slices[f] = {str(v): s for v, s in enumerate(m["slices"])}
     acc = float(((p > 0.5) == (y > 0.5)).mean())
     eps = 1e-7
     ll = float(-(y * np.log(p + eps) + (1 - y) * np.log(1 - p + eps)).mean())
     res = {"accuracy": acc, "auc": _auc(p, y), "log_loss": ll, "eval_rows": int(len(y)),
-           "baseline_accuracy": float(max(y.mean(), 1 - y.mean())), "blessed": acc >= threshold}
+           "baseline_accuracy": float(max(y.mean(), 1 - y.mean())), "blessed": acc >= threshold,
+           "path": path, "auc_bucketed": m["overall"]["auc_bucketed"], "slices": slices}
     _write_json(root / "evaluator" / "metrics.json", res)
     return res
 
@@ -265,10 +319,14 @@ def main(argv=None) -> int:
     ap.add_argument("--raw", default=None)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--batch", type=int, default=40)
+    ap.add_argument("--eval-every", type=int, default=0, help="trainer: evaluate the eval split every K steps")
+    ap.add_argument("--slice-by", default="trip_start_hour",
+                    help="evaluator: comma-separated wide features to slice the metrics by ('' = none)")
     a = ap.parse_args(argv)
     fn = {"example_gen": lambda: example_gen(a.root, a.raw), "statistics_gen": lambda: statistics_gen(a.root),
           "schema_gen": lambda: schema_gen(a.root), "transform": lambda: transform(a.root),
-          "trainer": lambda: trainer(a.root, a.steps, a.batch), "evaluator": lambda: evaluator(a.root),
+          "trainer": lambda: trainer(a.root, a.steps, a.batch, eval_every=a.eval_every),
+          "evaluator": lambda: evaluator(a.root, slice_by=tuple(f for f in a.slice_by.split(",") if f)),
           "pusher": lambda: pusher(a.root)}[a.component]
     print(json.dumps(fn(), default=float)[:2000], flush=True)
     return 0
