@@ -6,6 +6,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -42,38 +43,54 @@ static inline T* P(u p) {
 }
 static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 
-// deterministic mode: one flag per kernel translation unit (common.h HOPSX_DET_TU)
-extern "C" int hopsx_det_set_conv_mfma(int);
-extern "C" unsigned hopsx_det_lost_conv_mfma();
-extern "C" int hopsx_det_set_loss(int);
-extern "C" unsigned hopsx_det_lost_loss();
-extern "C" int hopsx_det_set_gemm(int);
-extern "C" unsigned hopsx_det_lost_gemm();
-extern "C" int hopsx_det_set_norm(int);
-extern "C" unsigned hopsx_det_lost_norm();
-extern "C" int hopsx_det_set_pool(int);
-extern "C" unsigned hopsx_det_lost_pool();
-extern "C" int hopsx_det_set_conv(int);
-extern "C" unsigned hopsx_det_lost_conv();
-extern "C" int hopsx_det_set_elementwise(int);
-extern "C" unsigned hopsx_det_lost_elementwise();
-extern "C" int hopsx_det_set_rowreduce(int);
-extern "C" unsigned hopsx_det_lost_rowreduce();
-extern "C" int hopsx_det_set_wgrad_glds(int);
-extern "C" unsigned hopsx_det_lost_wgrad_glds();
+// The kernel translation units with per-unit device state (common.h), one table: HOPSX_DET_TU(tag) units
+// have deterministic-mode state (and debug-check records), HOPSX_DBG_TU(tag) units debug-check records only.
+// The declarations, set_deterministic, det_lost and dbg_read below are generated from it.
+#define HOPSX_DET_TUS(X) \
+  X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
+#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval)
+#define X(tag)                              \
+  extern "C" int hopsx_det_set_##tag(int);  \
+  extern "C" unsigned hopsx_det_lost_##tag();
+HOPSX_DET_TUS(X)
+#undef X
+#define X(tag) extern "C" int hopsx_dbg_read_##tag(unsigned* out);
+HOPSX_DBG_TUS(X)
+#undef X
 
-extern "C" int hopsx_dbg_read_conv_mfma(unsigned* out);
-extern "C" int hopsx_dbg_read_loss(unsigned* out);
-extern "C" int hopsx_dbg_read_gemm(unsigned* out);
-extern "C" int hopsx_dbg_read_norm(unsigned* out);
-extern "C" int hopsx_dbg_read_pool(unsigned* out);
-extern "C" int hopsx_dbg_read_conv(unsigned* out);
-extern "C" int hopsx_dbg_read_elementwise(unsigned* out);
-extern "C" int hopsx_dbg_read_rowreduce(unsigned* out);
-extern "C" int hopsx_dbg_read_wgrad_glds(unsigned* out);
-extern "C" int hopsx_dbg_read_embedding(unsigned* out);
-extern "C" int hopsx_dbg_read_mnist_eval(unsigned* out);
-extern "C" int hopsx_dbg_read_taxi_eval(unsigned* out);
+// Launch-argument slots of the whole-step training kernels (runtime/launch_slots.py keeps the keys): the
+// argument vectors are converted once per change; a launch then crosses the binding with a slot id and the
+// stream only — at bench.py's 20 steps per launch the host path is inside the timed window while the GPU
+// waits.  def_arg_slots registers <name>_store(slot, p, iv, fv[, extra]) -> slot (an id out of range appends
+// a new slot) and <name>_slot(slot, stream) -> rc (an id out of range: hipErrorInvalidValue, no launch).
+struct ArgSlots {
+  std::vector<uint64_t> p;
+  std::vector<long> iv;
+  std::vector<float> fv;
+  long extra = 0;
+};
+template <bool EXTRA, class Launch>
+static void def_arg_slots(py::module_& m, const std::string& name, Launch launch) {
+  auto slots = std::make_shared<std::vector<ArgSlots>>();
+  auto store = [slots](int slot, std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, long extra) {
+    if (slot < 0 || slot >= (int)slots->size()) {
+      slots->push_back({});
+      slot = (int)slots->size() - 1;
+    }
+    (*slots)[slot] = ArgSlots{std::move(p), std::move(iv), std::move(fv), extra};
+    return slot;
+  };
+  if constexpr (EXTRA)
+    m.def((name + "_store").c_str(), store);
+  else
+    m.def((name + "_store").c_str(), [store](int slot, std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv) {
+      return store(slot, std::move(p), std::move(iv), std::move(fv), 0);
+    });
+  m.def((name + "_slot").c_str(), [slots, launch](int slot, u st) {
+    if (slot < 0 || slot >= (int)slots->size()) return (int)hipErrorInvalidValue;
+    return launch((*slots)[slot], S(st));
+  });
+}
 
 // the debug build (-DHOPSX_DEBUG=1) is the module _hopsx_ops_dbg (same sources, hx_check compiled in)
 #ifndef HOPSX_MODNAME
@@ -113,58 +130,26 @@ HX_PYMOD(HOPSX_MODNAME) {
   m.def("taxi_step2", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, long rows, u st) {
     return hopsx_taxi_step2(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), rows, S(st));
   });
-  // launch-argument slots of the v2 taxi step (models/widedeep.py _launch), as mnist_persist_store below
-  struct TaxiSlot {
-    std::vector<uint64_t> p;
-    std::vector<long> iv;
-    std::vector<float> fv;
-    long rows;
-  };
-  static std::vector<TaxiSlot> taxi_slots;
-  m.def("taxi_step2_store", [](int slot, std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, long rows) {
-    if (slot < 0 || slot >= (int)taxi_slots.size()) {
-      taxi_slots.push_back({});
-      slot = (int)taxi_slots.size() - 1;
-    }
-    taxi_slots[slot] = TaxiSlot{std::move(p), std::move(iv), std::move(fv), rows};
-    return slot;
-  });
-  m.def("taxi_step2_slot", [](int slot, u st) {
-    if (slot < 0 || slot >= (int)taxi_slots.size()) return (int)hipErrorInvalidValue;
-    const TaxiSlot& a = taxi_slots[slot];
+  def_arg_slots<true>(m, "taxi_step2", [](const ArgSlots& a, hipStream_t st) {
     return hopsx_taxi_step2(a.p.data(), (int)a.p.size(), a.iv.data(), (int)a.iv.size(), a.fv.data(), (int)a.fv.size(),
-                            a.rows, S(st));
+                            a.extra, st);  // extra: the wide table's rows
   });
   m.def("widedeep_step_lds", [](std::vector<long> iv) { return hopsx_widedeep_step_lds(iv.data(), (int)iv.size()); });
   m.def("set_deterministic", [](int on) {
     int e = 0;
-    if (!e) e = hopsx_det_set_conv_mfma(on);
-    if (!e) e = hopsx_det_set_loss(on);
-    if (!e) e = hopsx_det_set_gemm(on);
-    if (!e) e = hopsx_det_set_norm(on);
-    if (!e) e = hopsx_det_set_pool(on);
-    if (!e) e = hopsx_det_set_conv(on);
-    if (!e) e = hopsx_det_set_elementwise(on);
-    if (!e) e = hopsx_det_set_rowreduce(on);
-    if (!e) e = hopsx_det_set_wgrad_glds(on);
+#define X(tag) \
+  if (!e) e = hopsx_det_set_##tag(on);
+    HOPSX_DET_TUS(X)
+#undef X
     return e;
   });
   m.attr("DEBUG") = HOPSX_DEBUG_BUILD;
   // device-side check records per translation unit: [(tag, failures, line, workgroup, thread)], cleared
   m.def("dbg_read", []() {
     static const std::pair<const char*, int (*)(unsigned*)> tus[] = {
-    {"conv_mfma", hopsx_dbg_read_conv_mfma},
-    {"loss", hopsx_dbg_read_loss},
-    {"gemm", hopsx_dbg_read_gemm},
-    {"norm", hopsx_dbg_read_norm},
-    {"pool", hopsx_dbg_read_pool},
-    {"conv", hopsx_dbg_read_conv},
-    {"elementwise", hopsx_dbg_read_elementwise},
-    {"rowreduce", hopsx_dbg_read_rowreduce},
-    {"wgrad_glds", hopsx_dbg_read_wgrad_glds},
-    {"embedding", hopsx_dbg_read_embedding},
-    {"mnist_eval", hopsx_dbg_read_mnist_eval},
-    {"taxi_eval", hopsx_dbg_read_taxi_eval},
+#define X(tag) {#tag, hopsx_dbg_read_##tag},
+        HOPSX_DBG_TUS(X)
+#undef X
     };
     std::vector<std::tuple<std::string, unsigned, unsigned, unsigned, unsigned>> out;
     for (const auto& t : tus) {
@@ -177,43 +162,18 @@ HX_PYMOD(HOPSX_MODNAME) {
   });
   m.def("det_lost", []() {
     unsigned n = 0;
-    n += hopsx_det_lost_conv_mfma();
-    n += hopsx_det_lost_loss();
-    n += hopsx_det_lost_gemm();
-    n += hopsx_det_lost_norm();
-    n += hopsx_det_lost_pool();
-    n += hopsx_det_lost_conv();
-    n += hopsx_det_lost_elementwise();
-    n += hopsx_det_lost_rowreduce();
-    n += hopsx_det_lost_wgrad_glds();
+#define X(tag) n += hopsx_det_lost_##tag();
+    HOPSX_DET_TUS(X)
+#undef X
     return n;
   });
   m.def("mnist_persist", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, u st) {
     return hopsx_mnist_persist(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(),
                                S(st));
   });
-  // launch-argument slots of the persistent step (runtime/persist.py): the argument vectors are converted
-  // once per change; a launch then crosses the binding with a slot id and the stream only — at bench.py's
-  // 20 steps per launch the host path is inside the timed window while the GPU waits
-  struct PersistSlot {
-    std::vector<uint64_t> p;
-    std::vector<long> iv;
-    std::vector<float> fv;
-  };
-  static std::vector<PersistSlot> persist_slots;
-  m.def("mnist_persist_store", [](int slot, std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv) {
-    if (slot < 0 || slot >= (int)persist_slots.size()) {
-      persist_slots.push_back({});
-      slot = (int)persist_slots.size() - 1;
-    }
-    persist_slots[slot] = PersistSlot{std::move(p), std::move(iv), std::move(fv)};
-    return slot;
-  });
-  m.def("mnist_persist_slot", [](int slot, u st) {
-    if (slot < 0 || slot >= (int)persist_slots.size()) return (int)hipErrorInvalidValue;
-    const PersistSlot& a = persist_slots[slot];
+  def_arg_slots<false>(m, "mnist_persist", [](const ArgSlots& a, hipStream_t st) {
     return hopsx_mnist_persist(a.p.data(), (int)a.p.size(), a.iv.data(), (int)a.iv.size(), a.fv.data(),
-                               (int)a.fv.size(), S(st));
+                               (int)a.fv.size(), st);
   });
   // forward-only inference of the flagship model over n resident images (runtime/persist_eval.py)
   m.def("mnist_eval", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, u st) {

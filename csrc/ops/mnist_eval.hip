@@ -25,17 +25,25 @@
 // grid size).  A label outside [0, 10) is reported through hx_guard, selects no logit, and gives loss 0 /
 // hit 0.  The launch path allocates nothing, synchronises nothing and issues no memset: capture-safe.
 #include "common.h"
+#include "mnist_cnn.h"
+#include "wg_prims.h"
 
 namespace mnistev {
+// Shared with the training kernel by construction, not by comment: the device vocabulary (f2bf_hw, lds8,
+// mma32) and the model geometry (layer sizes, PH / NPOS / KIN, the W1S / W2S / C1S / PLS row strides of
+// the images the MFMA fragments are read from).  The LDS map, the tile size and Args below are this
+// kernel's own.
+using namespace wgp;
+using namespace mnist_cnn;
 
 constexpr int TB = 32;  // images per tile
-constexpr int C1 = 32, C2 = 64, HID = 128, NCLS = 10;
-constexpr int PH = 13, NPOS = PH * PH;  // pooled positions
-constexpr int KIN = NPOS * C2;          // 10816 fc1 inputs (NHWC flatten: (ph*13 + pw)*64 + c)
 constexpr int IMG = 28 * 28;
 
-// LDS row strides (bf16 elements), padded by 16 B against bank conflicts of the fragment reads
-constexpr int W1S = 72, W2S = 136, C1S = 40, PLS = 72;
+// (mnist_cnn.h states the stride rule; this is what the addressing below relies on)
+static_assert(KIN == NPOS * C2 && 2 * PH + 2 == 28, "13x13 pooled positions of 64 channels cover the image");
+static_assert(W1S >= C2 && W2S >= 4 * C1 && C1S >= C1 && PLS >= C2, "a row holds its K extent");
+static_assert(W1S % 8 == 0 && W2S % 8 == 0 && C1S % 8 == 0 && PLS % 8 == 0, "fragment reads are 16-B loads");
+
 constexpr int HS = 132;  // f32 row stride of the fc1 output tile
 
 // LDS map (bytes, every offset a multiple of 16)
@@ -71,14 +79,6 @@ struct Args {
   float xscale, xshift;
   int ntiles;
 };
-
-// fp32 -> bf16 round-to-nearest-even by the gfx950 conversion instruction (v_cvt_pk_bf16_f32):
-// the same bits as common.h's f2bf for every finite value
-__device__ __forceinline__ bf16_raw f2bf(float f) { return __builtin_bit_cast(bf16_raw, (__bf16)f); }
-__device__ __forceinline__ bf16x8 lds8(const bf16_raw* p) { return *(const bf16x8*)p; }
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
               v = fmaf(xi[py * 4 + px + 1], k1, v);
               v = fmaf(xi[(py + 1) * 4 + px], k2, v);
               v = fmaf(xi[(py + 1) * 4 + px + 1], k3, v);
-              A1[(b * 9 + py * 3 + px) * C1S + ci] = f2bf(fmaxf(v, 0.f));
+              A1[(b * 9 + py * 3 + px) * C1S + ci] = f2bf_hw(fmaxf(v, 0.f));
             }
         }
       }
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
           for (int j = 0; j < 4; ++j) {
             const bf16x8 bfr = lds8(W2 + (j * 16 + fr) * W2S + kk * 32 + fq * 8);
 #pragma unroll
-            for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mfma(af[ii], bfr, acc[ii][j]);
+            for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mma32(af[ii], bfr, acc[ii][j]);
           }
         }
 #pragma unroll
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
             const float bias = CB2[co];
             float best = 0.f;  // the window's values are relu outputs
 #pragma unroll
-            for (int r = 0; r < 4; ++r) best = fmaxf(best, bf2f(f2bf(fmaxf(acc[ii][j][r] + bias, 0.f))));
-            POOL[b * PLS + co] = f2bf(best);
+            for (int r = 0; r < 4; ++r) best = fmaxf(best, bf2f(f2bf_hw(fmaxf(acc[ii][j][r] + bias, 0.f))));
+            POOL[b * PLS + co] = f2bf_hw(best);
           }
       }
       __syncthreads();
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) hacc[i][jj] = mfma(af[i], bfr[jj], hacc[i][jj]);
+          for (int jj = 0; jj < 2; ++jj) hacc[i][jj] = mma32(af[i], bfr[jj], hacc[i][jj]);
       }
     }
     // ---- head: fc1 bias + relu (fp32) -> LDS (the conv1 tile's last readers passed the barrier above) ----

@@ -53,14 +53,16 @@
 // Determinism: no float atomics anywhere — every cross-workgroup sum is a fixed-order loop, so two
 // runs from the same state are bit-identical.
 #include "common.h"
+#include "mnist_cnn.h"
 #include "optim_core.h"
+#include "wg_prims.h"
 
 namespace mnistp {
+using namespace wgp;
+using namespace mnist_cnn;  // layer sizes, PH / NPOS / KIN, the W1S / W2S / C1S / PLS row strides
 
 constexpr int B = 32;  // images per step
-constexpr int C1 = 32, C2 = 64, HID = 128, NCLS = 10;
-constexpr int PH = 13, NPOS = PH * PH;  // pooled positions = position workgroups
-constexpr int KIN = NPOS * C2;          // 10816 fc1 inputs (NHWC flatten: (ph*13 + pw)*64 + c)
+// (one position workgroup per pooled position: NPOS of them)
 constexpr int NCONV = C2 * 128 + C2 + C1 * 4 + C1;  // 8416 conv params: [w2 | b2 | w1 | b1]
 constexpr int OFF_B2 = C2 * 128, OFF_W1 = OFF_B2 + C2, OFF_B1 = OFF_W1 + C1 * 4;
 constexpr int SLICE = 52, NSLICE = (NCONV + SLICE - 1) / SLICE;  // 162 slice owners
@@ -86,8 +88,9 @@ constexpr int TGB_N = NHEAD * (HID / 2);  // 2048 granules (16 KB) per parity
 constexpr int TG_WORDS = 2 * 2 * TGB_N;   // 32-bit words of the tag region
 static_assert(FL_WORDS % 2 == 0 && TGB_N % 256 == 0, "granules are 8-B aligned; every thread owns TGB_N / 256");
 
-// LDS row strides (bf16 elements), padded by 16 B against bank conflicts of the fragment reads
-constexpr int W1S = 72, W2S = 136, C1S = 40, PLS = 72, DHS = 136, DCS = 136;
+// LDS row strides (bf16 elements) of the backward-only images, by mnist_cnn.h's rule
+constexpr int DHS = row_stride(HID), DCS = row_stride(4 * B);
+static_assert(DHS == 136 && DCS == 136, "strides the kernel was tuned with");
 
 // position-workgroup LDS map (bytes, every offset a multiple of 16)
 constexpr int L_W1 = 0;                           // bf16 [128 n][W1S]   fc1 slice
@@ -140,10 +143,6 @@ static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU: 160 KiB LDS");
 static_assert(L_RED + NRED * SLICE * 4 <= L_SL && 2 * 32 * 5 * 4 <= 1024 * 4, "reduce scratch");
 static_assert(NRED * 13 <= 256 && NSLICE * SLICE >= NCONV && NSLICE <= NPOS, "slice geometry");
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned __attribute__((address_space(1))) gu32;
-typedef unsigned long long __attribute__((address_space(1))) gu64;
-
 struct Args {
   float* master;      // arena fp32 parameters
   bf16_raw* shadow;   // arena bf16 copy the other kernels read
@@ -192,47 +191,10 @@ struct Args {
   unsigned* xflag[XMAX];        // flag pages of ranks 0..world-1
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7fffffff, 0x00020000);
-}
-// write-through (sc1) 16-B store / sc1 16-B load (L1 bypass): the hand-off payload path
-__device__ __forceinline__ void st_sc1(__amdgpu_buffer_rsrc_t r, int byte_off, f32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r, byte_off, 0, 16);
-}
-__device__ __forceinline__ void st_sc1x2(__amdgpu_buffer_rsrc_t r, int byte_off, float x, float y) {
-  typedef int v2i __attribute__((ext_vector_type(2)));
-  __builtin_amdgcn_raw_buffer_store_b64((v2i){__float_as_int(x), __float_as_int(y)}, r, byte_off, 0, 16);
-}
-__device__ __forceinline__ f32x4 ld_sc1(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 16));
-}
-__device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void flag_store(unsigned* f, unsigned v) {
-  __hip_atomic_store((gu32*)f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned flag_load(const unsigned* f) {
-  return __hip_atomic_load((gu32*)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// Payload path of the hand-offs: write-through 16-B / 8-B stores and L1-bypassing 16-B loads (bst16<SC1>,
+// bst8<SC1>, bld16<SC1>); cross-rank exchange path: the same family at system scope (<SYS>); flag words:
+// flag_store / flag_load (agent scope), xflag_store / xflag_load (system scope).  All in wg_prims.h.
 
-// system-scope (sc0 sc1) 16-B / 4-B buffer store and load: the cross-rank exchange path
-__device__ __forceinline__ void st_sys(__amdgpu_buffer_rsrc_t r, int byte_off, f32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r, byte_off, 0, 17);
-}
-__device__ __forceinline__ void st_sys1(__amdgpu_buffer_rsrc_t r, int byte_off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, byte_off, 0, 17);
-}
-__device__ __forceinline__ f32x4 ld_sys(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 17));
-}
-__device__ __forceinline__ float ld_sys1(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 17));
-}
-__device__ __forceinline__ void xflag_store(unsigned* f, unsigned v) {
-  __hip_atomic_store((gu32*)f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ unsigned xflag_load(const unsigned* f) {
-  return __hip_atomic_load((gu32*)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 // slot a push lands in: the producer's rank (loopback: the simulated peer's, so every slot fills)
 __device__ __forceinline__ int xslot(const Args& a, int peer) { return a.loopback ? peer : a.rank; }
 
@@ -382,22 +344,6 @@ __device__ __forceinline__ float adadelta(float w, float g, float& s1, float& s2
 
 __device__ __forceinline__ unsigned ecode(int phase, int s) {
   return 0x80000000u | ((unsigned)phase << 24) | (((unsigned)s & 0xFFFu) << 12) | (blockIdx.x & 0xFFFu);
-}
-
-// fp32 -> bf16 round-to-nearest-even by the gfx950 conversion instruction (v_cvt_pk_bf16_f32):
-// the same bits as common.h's f2bf for every finite value, one instruction instead of five
-__device__ __forceinline__ bf16_raw f2bf(float f) { return __builtin_bit_cast(bf16_raw, (__bf16)f); }
-
-__device__ __forceinline__ bf16x8 lds8(const bf16_raw* p) { return *(const bf16x8*)p; }
-// transposed fragment read (ds_read_b64_tr_b16): this lane addresses row (k) 8*fq + tq (p1) and
-// 8*fq + tq + 4 (p2), 4 consecutive columns 4*tp..; the result holds column (lane & 15)'s 8 k values
-__device__ __forceinline__ bf16x8 lds_tr(const bf16_raw* p1, const bf16_raw* p2) {
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4_ptr)(p1));
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4_ptr)(p2));
-  return (bf16x8){v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-}
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 __device__ __forceinline__ long conv_idx(const Args& a, int j) {
@@ -574,11 +520,11 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         wm[ii][j][r] = a.master[ai];
         g1[ii][j][r] = a.s1[ai];
         g2[ii][j][r] = a.s2[ai];
-        W1[n * W1S + co] = f2bf(wm[ii][j][r]);
+        W1[n * W1S + co] = f2bf_hw(wm[ii][j][r]);
       }
   // ---- conv parameters (every position needs all of them) ----
   auto put_conv = [&](int j, float v) {
-    if (j < OFF_B2) W2[(j >> 7) * W2S + (j & 127)] = f2bf(v);
+    if (j < OFF_B2) W2[(j >> 7) * W2S + (j & 127)] = f2bf_hw(v);
     else if (j < OFF_W1) CB2[j - OFF_B2] = v;
     else if (j < OFF_B1) CW1[j - OFF_W1] = v;
     else CB1[j - OFF_B1] = v;
@@ -672,7 +618,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
             v = fmaf(xi[py][px + 1], k1, v);
             v = fmaf(xi[py + 1][px], k2, v);
             v = fmaf(xi[py + 1][px + 1], k3, v);
-            C1[(b * 9 + py * 3 + px) * C1S + ci] = f2bf(fmaxf(v, 0.f));
+            C1[(b * 9 + py * 3 + px) * C1S + ci] = f2bf_hw(fmaxf(v, 0.f));
           }
       }
     }
@@ -716,7 +662,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mfma(af[kk & 1][ii], bfr[kk & 1][j], acc[ii][j]);
+          for (int ii = 0; ii < 2; ++ii) acc[ii][j] = mma32(af[kk & 1][ii], bfr[kk & 1][j], acc[ii][j]);
       }
       bf16_raw pv[2][4];
       unsigned char av[2][4];
@@ -728,7 +674,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           int bi = 0;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = bf2f(f2bf(fmaxf(acc[ii][j][r] + bias[j], 0.f)));  // bf16 conv output, as unfused
+            const float v = bf2f(f2bf_hw(fmaxf(acc[ii][j][r] + bias[j], 0.f)));  // bf16 conv output, as unfused
             if (v > best) {
               best = v;
               bi = r;
@@ -741,7 +687,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
             best = 0.f;
             bi = 0xFF;
           }
-          pv[ii][j] = f2bf(best);
+          pv[ii][j] = f2bf_hw(best);
           av[ii][j] = (unsigned char)bi;
         }
       // (the stores after all the math: a store between two reads would be waited out with them)
@@ -777,7 +723,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma(af[kk][i], bfr[kk][jj], acc[i][jj]);
+          for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mma32(af[kk][i], bfr[kk][jj], acc[i][jj]);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -793,7 +739,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       for (int k = 0; k < 4; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) st_sc1(R, (tid + 256 * k) * 16, v[k]);
+      for (int k = 0; k < 4; ++k) bst16<SC1>(R, (tid + 256 * k) * 16, v[k]);
       drain();
       __syncthreads();
       if (tid == 0) flag_store(a.flags + FL_A + p, ep);
@@ -807,7 +753,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       const f32x4 f = __builtin_bit_cast(f32x4, lds_tr(POOL + (8 * fq + tq) * PLS + c0, POOL + (8 * fq + tq + 4) * PLS + c0));
       for (int r = 0; r < a.world; ++r) {
         if (r == a.rank) continue;
-        st_sys(rsrc(a.xbuf[r] + XO_POOL + (par * XMAX + xslot(a, r)) * XS_POOL + (long)p * 4096), (w * 64 + lane) * 16, f);
+        bst16<SYS>(rsrc(a.xbuf[r] + XO_POOL + (par * XMAX + xslot(a, r)) * XS_POOL + (long)p * 4096), (w * 64 + lane) * 16, f);
       }
       // (flags raised after the B wait: by then the stores have long completed, so the drain is free)
     }
@@ -849,9 +795,9 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int idx = tid + 256 * k, b = idx >> 5, n4 = idx & 31;
-        const f32x4 v = ld_sc1(R, (b * PAY + PAY_DH + n4 * 4) * 4);
+        const f32x4 v = bld16<SC1>(R, (b * PAY + PAY_DH + n4 * 4) * 4);
         *(bf16x4*)(DH + b * DHS + n4 * 4) =
-            (bf16x4){(short)f2bf(v[0]), (short)f2bf(v[1]), (short)f2bf(v[2]), (short)f2bf(v[3])};
+            (bf16x4){(short)f2bf_hw(v[0]), (short)f2bf_hw(v[1]), (short)f2bf_hw(v[2]), (short)f2bf_hw(v[3])};
       }
     }
     __syncthreads();
@@ -880,7 +826,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dp[i] = mfma(da[kk][i], db4[kk], dp[i]);
+        for (int i = 0; i < 2; ++i) dp[i] = mma32(da[kk][i], db4[kk], dp[i]);
     }
     // (no barrier: the phases up to the fc1 Adadelta write neither DH, POOL nor W1)
     // ---- dropout / max-pool / relu backward -> dconv2[(b,q)][co]; conv2 bias gradient ----
@@ -893,7 +839,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         for (int r = 0; r < 4; ++r) {
           const int b = i * 16 + fq * 4 + r;
           const int am = amv[i][r];
-          const bf16_raw gb = am != 0xFF ? f2bf(dp[i][r] * inv) : (bf16_raw)0;
+          const bf16_raw gb = am != 0xFF ? f2bf_hw(dp[i][r] * inv) : (bf16_raw)0;
           db += bf2f(gb);
           // the image's 4 window taps are adjacent columns of row co: one 8-byte store
           *(bf16x4*)(DC2 + co * DCS + b * 4) = (bf16x4){(short)(am == 0 ? gb : 0), (short)(am == 1 ? gb : 0),
@@ -933,7 +879,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = mfma(af[kk & 1], bfr[kk & 1][j], acc[j]);
+        for (int j = 0; j < 8; ++j) acc[j] = mma32(af[kk & 1], bfr[kk & 1][j], acc[j]);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j)
@@ -970,7 +916,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         for (int k = 0; k < NK; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 0; k < NK; ++k) st_sc1(R, (tid + 256 * k) * 16, v[k]);
+        for (int k = 0; k < NK; ++k) bst16<SC1>(R, (tid + 256 * k) * 16, v[k]);
       }
       f32x4 acc[4][4];  // [M tile mh*4+i][tap t (N tile 2t+h)]
 #pragma unroll
@@ -982,7 +928,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) acc[i][t] = mfma(af[kk][i], bfr[kk][t], acc[i][t]);
+          for (int i = 0; i < 4; ++i) acc[i][t] = mma32(af[kk][i], bfr[kk][t], acc[i][t]);
       // relu' of conv1: the 36 conv1 outputs of this lane's (b, ci), all in flight while the MFMAs run
       bf16_raw c1v[4][9];
 #pragma unroll
@@ -1007,7 +953,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) gw[ii][j] = mfma(wa[ii], wb[j], (f32x4){0.f, 0.f, 0.f, 0.f});
+          for (int j = 0; j < 4; ++j) gw[ii][j] = mma32(wa[ii], wb[j], (f32x4){0.f, 0.f, 0.f, 0.f});
       }
       float gk[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
       f32x4 xq[2][4];  // image b's 4x4 input patch, read one image ahead of its use
@@ -1062,7 +1008,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     {  // publish C, part 2: the 224 small gradients [b2 | conv1 w | conv1 b]; every wave drains both parts
       const auto R = rsrc(a.slabC + ((long)par * NPOS + p) * NCONV);
       const int idx = OFF_B2 / 4 + tid;
-      if (idx < NCONV / 4) st_sc1(R, idx * 16, *(const f32x4*)(STG + idx * 4));
+      if (idx < NCONV / 4) bst16<SC1>(R, idx * 16, *(const f32x4*)(STG + idx * 4));
       drain();
       __syncthreads();
       if (tid == 0) flag_store(a.flags + FL_C + p, ep);
@@ -1089,7 +1035,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         for (int k = 0; k < NKC; ++k) v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
         const unsigned pend = !act ? 0u : (g + NRED * (NKC - 1) < NPOS ? (1u << NKC) - 1u : (1u << (NKC - 1)) - 1u);
         gather_rows<NKC>(a.flags + FL_C + lp, mine, act ? (g - g0) * NKC : 0, pend, ep, a.err, ecode(3, s), s_ok + 2,
-                         a.tmo, [&](int k) { v[k] = ld_sc1(R, ((g + NRED * k) * NCONV + e0 + 4 * j) * 4); });
+                         a.tmo, [&](int k) { v[k] = bld16<SC1>(R, ((g + NRED * k) * NCONV + e0 + 4 * j) * 4); });
         stamp(a, s, 7);  // (the partials' load is inside the wait in this form)
         // every lane names its partial registers here, so the compiler waits for the loads on every path into the
         // sum (the sum's lanes wait here anyway).  Left to the conditional sum, its bookkeeping keeps them pending
@@ -1120,7 +1066,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
           for (int k = 0; k < NK; ++k) {
             const int pp = g + NRED * k;
-            v[k] = pp < NPOS ? ld_sc1(R, (pp * NCONV + e0 + 4 * j) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            v[k] = pp < NPOS ? bld16<SC1>(R, (pp * NCONV + e0 + 4 * j) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
           }
 #pragma unroll
           for (int k = 0; k < NK; ++k) acc += v[k];
@@ -1141,7 +1087,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           if (tid < SLICE) {
             for (int r = 0; r < a.world; ++r) {
               if (r == a.rank) continue;
-              st_sys1(rsrc(a.xbuf[r] + XO_CONV + (par * XMAX + xslot(a, r)) * XS_CONV), e * 4, gs);
+              bst4<SYS>(rsrc(a.xbuf[r] + XO_CONV + (par * XMAX + xslot(a, r)) * XS_CONV), e * 4, gs);
             }
           }
           drain();
@@ -1152,7 +1098,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           const auto X = rsrc(a.xbuf[a.rank] + XO_CONV + (long)par * XMAX * XS_CONV);
           float v[XMAX];  // every peer's value in flight before the rank-order sum
 #pragma unroll
-          for (int r = 0; r < XMAX; ++r) v[r] = r < a.world && r != a.rank ? ld_sys1(X, (int)(r * XS_CONV) + e * 4) : gs;
+          for (int r = 0; r < XMAX; ++r) v[r] = r < a.world && r != a.rank ? bld4<SYS>(X, (int)(r * XS_CONV) + e * 4) : gs;
           float t = 0.f;
 #pragma unroll
           for (int r = 0; r < XMAX; ++r)
@@ -1172,7 +1118,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         unsigned char* D = (unsigned char*)a.slabD + (long)par * D_BYTES;
         if (e < OFF_B2) {
           if (!(tid & 1))
-            __hip_atomic_store((gu32*)(D + e * 2), (unsigned)f2bf(wn) | ((unsigned)f2bf(wnext) << 16),
+            __hip_atomic_store((gu32*)(D + e * 2), (unsigned)f2bf_hw(wn) | ((unsigned)f2bf_hw(wnext) << 16),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (e < NCONV) {
           __hip_atomic_store((gu32*)(D + D_F32 + (e - OFF_B2) * 4), __float_as_uint(wn), __ATOMIC_RELAXED,
@@ -1219,10 +1165,10 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         } else {
 #pragma unroll
           for (int ii = 0; ii < 2; ++ii)
-            af[b][ii] = __builtin_bit_cast(bf16x8, ld_sys(XD, (int)(r * XS_DHT) + ((2 * w + ii) * 64 + lane) * 16));
+            af[b][ii] = __builtin_bit_cast(bf16x8, bld16<SYS>(XD, (int)(r * XS_DHT) + ((2 * w + ii) * 64 + lane) * 16));
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            bfr[b][j] = __builtin_bit_cast(bf16x8, ld_sys(XP, (int)(r * XS_POOL) + (j * 64 + lane) * 16));
+            bfr[b][j] = __builtin_bit_cast(bf16x8, bld16<SYS>(XP, (int)(r * XS_POOL) + (j * 64 + lane) * 16));
         }
       };
 #pragma unroll
@@ -1236,7 +1182,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-              gw[ii][j] += mfma(af[r % PF][ii], bfr[r % PF][j], (f32x4){0.f, 0.f, 0.f, 0.f});
+              gw[ii][j] += mma32(af[r % PF][ii], bfr[r % PF][j], (f32x4){0.f, 0.f, 0.f, 0.f});
         }
       }
     }
@@ -1249,7 +1195,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           wm[ii][j][r] = adadelta(wm[ii][j][r], gw[ii][j][r] * hp.gscale, g1[ii][j][r], g2[ii][j][r], hp);
-          W1[((2 * w + ii) * 16 + fq * 4 + r) * W1S + j * 16 + fr] = f2bf(wm[ii][j][r]);
+          W1[((2 * w + ii) * 16 + fq * 4 + r) * W1S + j * 16 + fr] = f2bf_hw(wm[ii][j][r]);
         }
     if (s + 1 < a.nsteps) draw_keep(s + 1);  // KEEP is next read after the D wait's barrier
     stamp(a, s, 9);
@@ -1264,8 +1210,8 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       constexpr int NF = (NCONV - OFF_B2) / 4;   // 56 16-B chunks of fp32
       f32x4 dv[NB / 256 + 1];
 #pragma unroll
-      for (int k = 0; k < NB / 256; ++k) dv[k] = ld_sc1(R, (tid + 256 * k) * 16);
-      dv[NB / 256] = tid < NF ? ld_sc1(R, D_F32 + tid * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < NB / 256; ++k) dv[k] = bld16<SC1>(R, (tid + 256 * k) * 16);
+      dv[NB / 256] = tid < NF ? bld16<SC1>(R, D_F32 + tid * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < NB / 256; ++k) {
         const int c = tid + 256 * k;  // chunk c: conv2 row c >> 4, 8 values from column (c & 15) * 8
@@ -1293,7 +1239,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         a.master[ai] = wm[ii][j][r];
         a.s1[ai] = g1[ii][j][r];
         a.s2[ai] = g2[ii][j][r];
-        a.shadow[ai] = f2bf(wm[ii][j][r]);
+        a.shadow[ai] = f2bf_hw(wm[ii][j][r]);
       }
   if (owner && tid < SLICE) {
     const int e = p * SLICE + tid;
@@ -1302,7 +1248,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       a.master[ci] = SLm[tid];
       a.s1[ci] = SL1[tid];
       a.s2[ci] = SL2[tid];
-      a.shadow[ci] = f2bf(SLm[tid]);
+      a.shadow[ci] = f2bf_hw(SLm[tid]);
     }
   }
   stamp(a, a.nsteps - 1, 14);  // (debug stamps: write-back issued)
@@ -1388,7 +1334,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
         const int pp = g + 8 * k;
-        v[k] = pp < NPOS ? ld_sc1(R, ((pp * B + i) * HID + n4 * 4) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        v[k] = pp < NPOS ? bld16<SC1>(R, ((pp * B + i) * HID + n4 * 4) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
       }
       f32x4 acc = v[0];
 #pragma unroll
@@ -1444,10 +1390,10 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
         // in front of it; the fp32 payload + flag below serve the heads' fc2 update and the DP push
         if (a.hand & 1)
           granule_store((unsigned long long*)(a.flags + FL_WORDS) + (par * NHEAD + i) * (HID / 2) + lane, ep,
-                        (unsigned)f2bf(dh[0]) | ((unsigned)f2bf(dh[1]) << 16));
+                        (unsigned)f2bf_hw(dh[0]) | ((unsigned)f2bf_hw(dh[1]) << 16));
         const auto R = rsrc(a.slabB + ((long)par * NHEAD + i) * PAY);
-        st_sc1x2(R, (PAY_DH + n0) * 4, dh[0], dh[1]);
-        st_sc1x2(R, (PAY_H + n0) * 4, h[0], h[1]);
+        bst8<SC1>(R, (PAY_DH + n0) * 4, dh[0], dh[1]);
+        bst8<SC1>(R, (PAY_H + n0) * 4, h[0], h[1]);
         float p0 = 0.f, p1 = 0.f;
 #pragma unroll
         for (int c = 0; c < NCLS; c += 2)
@@ -1455,8 +1401,8 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
             p0 = dl[c];
             p1 = dl[c + 1];
           }
-        if (lane < NCLS / 2) st_sc1x2(R, (PAY_DL + 2 * lane) * 4, p0, p1);
-        if (lane == NCLS / 2) st_sc1x2(R, PAY_LOSS * 4, __logf(se) + m - zy, am == y ? 1.f : 0.f);
+        if (lane < NCLS / 2) bst8<SC1>(R, (PAY_DL + 2 * lane) * 4, p0, p1);
+        if (lane == NCLS / 2) bst8<SC1>(R, PAY_LOSS * 4, __logf(se) + m - zy, am == y ? 1.f : 0.f);
         drain();
         if (lane == 0) flag_store(a.flags + FL_B + i, ep);
       }
@@ -1506,9 +1452,9 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
     {  // publish B (the tagged dh first, as in the one-wave form)
       if ((a.hand & 1) && tid < HID / 2)
         granule_store((unsigned long long*)(a.flags + FL_WORDS) + (par * NHEAD + i) * (HID / 2) + tid, ep,
-                      (unsigned)f2bf(PAYL[PAY_DH + 2 * tid]) | ((unsigned)f2bf(PAYL[PAY_DH + 2 * tid + 1]) << 16));
+                      (unsigned)f2bf_hw(PAYL[PAY_DH + 2 * tid]) | ((unsigned)f2bf_hw(PAYL[PAY_DH + 2 * tid + 1]) << 16));
       const auto R = rsrc(a.slabB + ((long)par * NHEAD + i) * PAY);
-      if (tid < PAY / 4) st_sc1(R, tid * 16, *(const f32x4*)(PAYL + tid * 4));
+      if (tid < PAY / 4) bst16<SC1>(R, tid * 16, *(const f32x4*)(PAYL + tid * 4));
       drain();
       __syncthreads();
       if (tid == 0) flag_store(a.flags + FL_B + i, ep);
@@ -1526,7 +1472,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
         const int idx = tid + 256 * k;
-        v[k] = idx < NHEAD * PAY / 4 ? ld_sc1(R, idx * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        v[k] = idx < NHEAD * PAY / 4 ? bld16<SC1>(R, idx * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
@@ -1562,7 +1508,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
         // head 0 pushes this replica's head gradients and dh^T (fc1-wgrad A fragments, bf16, the layout
         // the position workgroups read from their own LDS) to every peer
         bf16_raw* DS = (bf16_raw*)(smem + H_DHS);
-        for (int e = tid; e < B * HID; e += 256) DS[(e >> 7) * DHS + (e & 127)] = f2bf(ALL[(e >> 7) * PAY + PAY_DH + (e & 127)]);
+        for (int e = tid; e < B * HID; e += 256) DS[(e >> 7) * DHS + (e & 127)] = f2bf_hw(ALL[(e >> 7) * PAY + PAY_DH + (e & 127)]);
         __syncthreads();
         const int w = tid >> 6, fr = lane & 15, fq = lane >> 4, tq = fr >> 2, tp = fr & 3;
         f32x4 fd[2];
@@ -1576,12 +1522,12 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
           const int sl = xslot(a, r);
           const auto XG = rsrc(a.xbuf[r] + XO_FC2 + (par * XMAX + sl) * XS_FC2);
 #pragma unroll
-          for (int k = 0; k < NW; ++k) st_sys1(XG, (tid + 256 * k) * 4, gl[k]);
-          if (tid < HID) st_sys1(XG, (NCLS * HID + tid) * 4, gl[NW]);
-          if (tid < NCLS) st_sys1(XG, (NCLS * HID + HID + tid) * 4, gl[NW + 1]);
+          for (int k = 0; k < NW; ++k) bst4<SYS>(XG, (tid + 256 * k) * 4, gl[k]);
+          if (tid < HID) bst4<SYS>(XG, (NCLS * HID + tid) * 4, gl[NW]);
+          if (tid < NCLS) bst4<SYS>(XG, (NCLS * HID + HID + tid) * 4, gl[NW + 1]);
           const auto XD = rsrc(a.xbuf[r] + XO_DHT + (par * XMAX + sl) * XS_DHT);
 #pragma unroll
-          for (int ii = 0; ii < 2; ++ii) st_sys(XD, ((2 * w + ii) * 64 + lane) * 16, fd[ii]);
+          for (int ii = 0; ii < 2; ++ii) bst16<SYS>(XD, ((2 * w + ii) * 64 + lane) * 16, fd[ii]);
         }
         drain();
         __syncthreads();
@@ -1599,9 +1545,9 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
         const bool peer = r < a.world && r != a.rank;
         const int o = (int)(r * XS_FC2);
 #pragma unroll
-        for (int k = 0; k < NW; ++k) v[r][k] = peer ? ld_sys1(X, o + (tid + 256 * k) * 4) : gl[k];
-        v[r][NW] = peer && tid < HID ? ld_sys1(X, o + (NCLS * HID + tid) * 4) : gl[NW];
-        v[r][NW + 1] = peer && tid < NCLS ? ld_sys1(X, o + (NCLS * HID + HID + tid) * 4) : gl[NW + 1];
+        for (int k = 0; k < NW; ++k) v[r][k] = peer ? bld4<SYS>(X, o + (tid + 256 * k) * 4) : gl[k];
+        v[r][NW] = peer && tid < HID ? bld4<SYS>(X, o + (NCLS * HID + tid) * 4) : gl[NW];
+        v[r][NW + 1] = peer && tid < NCLS ? bld4<SYS>(X, o + (NCLS * HID + HID + tid) * 4) : gl[NW + 1];
       }
 #pragma unroll
       for (int r = 0; r < XMAX; ++r)
@@ -1637,21 +1583,21 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
       a.master[ai] = HW[j];
       a.s1[ai] = HW1[j];
       a.s2[ai] = HW2[j];
-      a.shadow[ai] = f2bf(HW[j]);
+      a.shadow[ai] = f2bf_hw(HW[j]);
     }
     if (tid < NCLS) {
       const long ai = a.off[7] + tid;
       a.master[ai] = HB2[tid];
       a.s1[ai] = HB2[16 + tid];
       a.s2[ai] = HB2[32 + tid];
-      a.shadow[ai] = f2bf(HB2[tid]);
+      a.shadow[ai] = f2bf_hw(HB2[tid]);
     }
     if (tid < HID) {
       const long ai = a.off[5] + tid;
       a.master[ai] = HB1[tid];
       a.s1[ai] = HB1[128 + tid];
       a.s2[ai] = HB1[256 + tid];
-      a.shadow[ai] = f2bf(HB1[tid]);
+      a.shadow[ai] = f2bf_hw(HB1[tid]);
     }
   }
 }

@@ -34,23 +34,35 @@
 // path allocates nothing, synchronises nothing and issues no memset (the accumulators are cleared by a
 // kernel of this file): capture-safe.
 #include "common.h"
+#include "taxi_wd.h"
+#include "wg_prims.h"
 
 namespace taxiev {
+// Shared with the training kernel by construction, not by comment: the device vocabulary (f2bf_hw, b2f,
+// the held MFMA forms) and the model geometry (NWIDE, D0..D4, the wide columns' cardinalities CARD, cdiv,
+// the fp32 bias / w4 map F_B0..F_W4 that both kernels stage the same way).  The W images, the LDS map,
+// the tile size and Args below are this kernel's own.
+using namespace wgp;
+using namespace taxi_wd;
 
 constexpr int NT = 256;      // 4 waves, one 16-row tile each per trip
 constexpr int TR = 16;       // rows per tile
-constexpr int NWIDE = 13;
-constexpr int D0 = 3, D1 = 100, D2 = 70, D3 = 48, D4 = 34;  // dense input + hidden widths (logits: 1)
 constexpr int WROWS = 6288;  // wide rows the LDS table holds (the model has 6,287)
 constexpr int NB = 1024;     // probability bins
 constexpr int SMAX = 128;    // slices
 constexpr float QSCALE = 16777216.f;  // 2^24 fixed point of the loss / probability sums
 
-// the 13 wide columns (models/widedeep.py wide_cardinalities): 4 buckets, 2 vocabularies, hour, day, month,
-// 2 census tracts, 2 community areas
-constexpr int CARD[NWIDE] = {10, 10, 10, 10, 1010, 1010, 24, 31, 12, 2000, 2000, 80, 80};
+// rows of the model's wide table: the 13 columns back to back
+constexpr int wide_rows() {
+  int t = 0;
+  for (int c = 0; c < NWIDE; ++c) t += CARD[c];
+  return t;
+}
+static_assert(wide_rows() == 6287 && wide_rows() <= WROWS, "the LDS wide table holds the model's rows");
+// columns that may be the slice column: at most SMAX values (not the vocabularies and census tracts); a
+// row's slice is its value in that column
+constexpr bool sliceable(int c) { return CARD[c] <= SMAX; }
 
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // layer: IN -> OUT.  IT input tiles of 16 (NK32 pairs for the x32 MFMA + one x16 tail), OT output tiles;
 // W image [16 OT][K] bf16 at byte offset LW, fp32 bias [16 OT] at float offset FB (both zero beyond OUT / IN)
@@ -65,14 +77,17 @@ struct Layer {
     return pos < 32 * NK32 ? 16 * (2 * (pos >> 5) + ((pos & 7) >> 2)) + 4 * ((pos & 31) >> 3) + (pos & 3) : pos;
   }
 };
-constexpr int F_B0 = 0, F_B1 = F_B0 + 16 * cdiv(D1, 16), F_B2 = F_B1 + 16 * cdiv(D2, 16),
-              F_B3 = F_B2 + 16 * cdiv(D3, 16), F_W4 = F_B3 + 16 * cdiv(D4, 16), F_MISC = F_W4 + 16 * cdiv(D4, 16),
-              F_END = F_MISC + 16;
+constexpr int F_MISC = F_W4_END, F_END = F_MISC + 16;  // b4 behind taxi_wd.h's bias / w4 map
 using L0 = Layer<D0, D1, 0, F_B0>;
 using L1 = Layer<D1, D2, L0::LW + L0::BYTES, F_B1>;
 using L2 = Layer<D2, D3, L1::LW + L1::BYTES, F_B2>;
 using L3 = Layer<D3, D4, L2::LW + L2::BYTES, F_B3>;
 static_assert(L1::IT == L0::OT && L2::IT == L1::OT && L3::IT == L2::OT, "a layer's input tiles are its producer's");
+// taxi_wd.h's map is laid out in whole output tiles of these layers; w4 is read as one f32x4 per lane
+// group and output tile of layer 3, so it spans L3's tiles too
+static_assert(F_B1 - F_B0 == 16 * L0::OT && F_B2 - F_B1 == 16 * L1::OT && F_B3 - F_B2 == 16 * L2::OT &&
+                  F_W4 - F_B3 == 16 * L3::OT && F_W4_END - F_W4 == 16 * L3::OT,
+              "bias / w4 map: whole output tiles");
 
 // LDS map (bytes, every offset a multiple of 16)
 constexpr int L_F = L3::LW + L3::BYTES;            // f32  biases, w4, b4
@@ -105,24 +120,9 @@ struct Args {
   long long slice_lo;       // global id of the slice column's value 0
 };
 
-// fp32 -> bf16 round-to-nearest-even by the gfx950 conversion instruction (as taxi_step.hip's f2b)
-__device__ __forceinline__ short f2b(float f) { return __builtin_bit_cast(short, (__bf16)f); }
-__device__ __forceinline__ float b2f(short v) { return __uint_as_float(((uint32_t)(uint16_t)v) << 16); }
-// The MFMA reads its A / B registers over its first cycles, and nothing interlocks a VALU write to them in
-// that window: with the activations living in registers, hipcc reused the last A register for an address
-// computation in the very next instruction after a 16x16x32 (`v_mfma ... v[118:121] ...; v_add_u32 v121, ...`)
-// and the product came out wrong.  The pad keeps A and B alive (and every later write to their registers
-// behind it) for 4 wait states after the issue; it is inside the string, where no pass can separate them.
-__device__ __forceinline__ f32x4 mma32(bf16x8 a, bf16x8 b, f32x4 c) {
-  f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  asm volatile("s_nop 3" : "+v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ f32x4 mma16(bf16x4 a, bf16x4 b, f32x4 c) {
-  f32x4 r = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-  asm volatile("s_nop 3" : "+v"(r) : "v"(a), "v"(b));
-  return r;
-}
+// MFMA: the activations of a row tile live in registers from layer to layer, across every MFMA, so this
+// kernel uses wg_prims.h's HELD forms (mma32_held / mma16_held: the operands stay alive for 4 wait states
+// after the issue).  Do not switch them to the plain forms: the products come out wrong.
 
 // W image of layer Ly from the shadow's row-major [OUT][IN]: k-permuted, zero beyond OUT / IN.  Every load
 // is issued before the first store (clamped addresses, masked values: no branch around a load)
@@ -194,12 +194,12 @@ __device__ __forceinline__ void layer(const unsigned char* smem, const bf16x4* i
     for (int kk = 0; kk < Ly::NK32; ++kk) {
       const bf16x4 lo = in[2 * kk], hi = in[2 * kk + 1];
       const bf16x8 b = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      acc = mma32(*(const bf16x8*)(wrow + 32 * kk + 8 * fq), b, acc);
+      acc = mma32_held(*(const bf16x8*)(wrow + 32 * kk + 8 * fq), b, acc);
     }
-    acc = mma16(*(const bf16x4*)(wrow + 32 * Ly::NK32 + 4 * fq), in[Ly::IT - 1], acc);
+    acc = mma16_held(*(const bf16x4*)(wrow + 32 * Ly::NK32 + 4 * fq), in[Ly::IT - 1], acc);
     const f32x4 bv = *(const f32x4*)(bias + 16 * ot + 4 * fq);
-    out[ot] = (bf16x4){f2b(fmaxf(acc[0] + bv[0], 0.f)), f2b(fmaxf(acc[1] + bv[1], 0.f)),
-                       f2b(fmaxf(acc[2] + bv[2], 0.f)), f2b(fmaxf(acc[3] + bv[3], 0.f))};
+    out[ot] = (bf16x4){(short)f2bf_hw(fmaxf(acc[0] + bv[0], 0.f)), (short)f2bf_hw(fmaxf(acc[1] + bv[1], 0.f)),
+                       (short)f2bf_hw(fmaxf(acc[2] + bv[2], 0.f)), (short)f2bf_hw(fmaxf(acc[3] + bv[3], 0.f))};
   }
 }
 
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(NT, 2) void taxi_eval_k(const Args a) {
 
     // ---- deep part ----
     bf16x4 a0 = {0, 0, 0, 0};
-    if (live && eg == 0) a0 = (bf16x4){f2b(cur.x[0]), f2b(cur.x[1]), f2b(cur.x[2]), 0};
+    if (live && eg == 0) a0 = (bf16x4){(short)f2bf_hw(cur.x[0]), (short)f2bf_hw(cur.x[1]), (short)f2bf_hw(cur.x[2]), 0};
     bf16x4 h1[L0::OT], h2[L1::OT], h3[L2::OT], h4[L3::OT];
     layer<L0>(smem, &a0, h1, lane);
     layer<L1>(smem, h1, h2, lane);
@@ -381,7 +381,7 @@ extern "C" int hopsx_taxi_eval(const uint64_t* p, int np, const long* iv, int ni
       if (c < scol) lo += CARD[c];
       total += CARD[c];
     }
-    if (CARD[scol] > SMAX || rows != total) return (int)hipErrorInvalidValue;  // vocabularies, census tracts
+    if (!sliceable(scol) || rows != total) return (int)hipErrorInvalidValue;  // vocabularies, census tracts
     a.slice_lo = lo;
     a.slice_card = CARD[scol];
   }

@@ -47,19 +47,20 @@
 
 #include "common.h"
 #include "optim_core.h"
+#include "taxi_wd.h"
+#include "wg_prims.h"
 
 namespace taxi2 {
+using namespace wgp;
+using namespace taxi_wd;  // NWIDE, D0..D4, cdiv, the fp32 bias / w4 map F_B0..F_W4
 
 constexpr int NT = 512;  // 8 waves: 2 per SIMD, 256 registers a lane for the owned optimizer state
 constexpr int NW = NT / 64;
 constexpr int NTW = 3;   // tile waves (batch tiles of 16 rows)
 constexpr int BP = 48;   // batch rows (B <= 48)
-constexpr int NWIDE = 13;
 constexpr int WJ = 13;  // wide rows per thread
 constexpr int MAXROWS = NT * WJ;
-constexpr int D0 = 3, D1 = 100, D2 = 70, D3 = 48, D4 = 34;  // dense input + hidden widths (logits: 1)
 
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int pad32(int x) { return (x + 31) & ~31; }
 // dW tile rounds a lane owns (the deep exchange payload's slots; = NSLOT below, checked there)
 constexpr int NSLOT_X = cdiv(cdiv(D4, 16) * cdiv(D3 + 1, 16), NT / 64) + cdiv(cdiv(D3, 16) * cdiv(D2 + 1, 16), NT / 64) +
@@ -82,9 +83,9 @@ constexpr int OFF_W2 = OFF_W1 + W1R * SA1;
 constexpr int OFF_W3 = OFF_W2 + W2R * SA2;
 constexpr int BF_END = OFF_W3 + W3R * SA3;
 constexpr int BF_BYTES = BF_END * 2;
-// ---- fp32 region (float offsets from BF_BYTES)
-constexpr int F_B0 = 0, F_B1 = F_B0 + 16 * cdiv(D1, 16), F_B2 = F_B1 + 16 * cdiv(D2, 16),
-              F_B3 = F_B2 + 16 * cdiv(D3, 16), F_W4 = F_B3 + 16 * cdiv(D4, 16), F_MISC = F_W4 + 48,
+// ---- fp32 region (float offsets from BF_BYTES): taxi_wd.h's bias / w4 map, then this kernel's own
+static_assert(F_W4_END == F_W4 + 48, "w4: three 16-wide tiles");
+constexpr int F_MISC = F_W4_END,
               F_RED = F_MISC + 16, F_DW4 = F_RED + 16, F_GV = F_DW4 + 3 * 48, F_IDT = F_GV + BP, F_LT = F_IDT + 16 * BP,
               F_GS = F_LT + 16 * BP, F_WTAB = F_GS + 16 * BP, F_VD = F_WTAB + MAXROWS, F_END = F_VD + 4;
 constexpr int LDS_BYTES = BF_BYTES + F_END * 4;
@@ -143,17 +144,7 @@ struct Args {
   unsigned* xflag[XMAX];       // flag pages of ranks 0..world-1
 };
 
-typedef __attribute__((address_space(3))) bf16x4* lds4_t;
-
-__device__ __forceinline__ bf16_raw f2b(float f) { return __builtin_bit_cast(bf16_raw, (__bf16)f); }
-__device__ __forceinline__ float b2f(short v) { return __uint_as_float(((uint32_t)(uint16_t)v) << 16); }
-__device__ __forceinline__ float rbf(float f) { return b2f((short)f2b(f)); }  // round to bf16
-__device__ __forceinline__ f32x4 mma32(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mma16(bf16x4 a, bf16x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-}
+__device__ __forceinline__ float rbf(float f) { return b2f((short)f2bf_hw(f)); }  // round to bf16
 // operand with K along the row: lane l takes row r0 + (l & 15), 8 (or 4) consecutive k
 __device__ __forceinline__ bf16x8 rd8(const bf16_raw* img, int S, int r0, int k0, int lane) {
   return *(const bf16x8*)(img + (r0 + (lane & 15)) * S + k0 + 8 * (lane >> 4));
@@ -166,23 +157,18 @@ __device__ __forceinline__ bf16x4 rd4(const bf16_raw* img, int S, int r0, int k0
 // lane-dependent branch.
 __device__ __forceinline__ bf16x4 tr4(const bf16_raw* img, int S, int k0, int c0, int lane) {
   const int i = lane & 15;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(img + (k0 + 4 * (lane >> 4) + (i >> 2)) * S + c0 + 4 * (i & 3)));
+  return lds_tr4(img + (k0 + 4 * (lane >> 4) + (i >> 2)) * S + c0 + 4 * (i & 3));
 }
 __device__ __forceinline__ bf16x8 tr8(const bf16_raw* img, int S, int k0, int c0, int lane) {
   const int i = lane & 15;
   const bf16_raw* p = img + (k0 + 8 * (lane >> 4) + (i >> 2)) * S + c0 + 4 * (i & 3);
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)p);
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(p + 4 * S));
-  return (bf16x8){v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
+  return lds_tr(p, p + 4 * S);
 }
 __device__ __forceinline__ void st4(bf16_raw* p, float a, float b, float c, float d) {
-  *(bf16x4*)p = (bf16x4){(short)f2b(a), (short)f2b(b), (short)f2b(c), (short)f2b(d)};
+  *(bf16x4*)p = (bf16x4){(short)f2bf_hw(a), (short)f2bf_hw(b), (short)f2bf_hw(c), (short)f2bf_hw(d)};
 }
 __device__ __forceinline__ float sel(bool c, float a, float b) { return c ? a : b; }
 
-// Workgroup barrier that waits only for LDS traffic: the next batch's loads stay in flight across
-// it (a __syncthreads() would drain them at every phase)
-__device__ __forceinline__ void bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // keeps the compiler from moving LDS accesses across it (this wave's own write -> read order)
 __device__ __forceinline__ void fence_c() { asm volatile("" ::: "memory"); }
 
@@ -253,32 +239,8 @@ static_assert(L0::NDW < NW && NW == 8, "tile map");
 constexpr int S3 = 0, S2 = S3 + R3, S1 = S2 + R2, S0 = S1 + R1, NSLOT = S0 + 1;
 static_assert(NSLOT == NSLOT_X, "exchange payload slots");
 
-// ---- cross-rank exchange primitives (DP): system-scope (sc0 sc1) buffer stores / loads on the uncached
-// exchange buffers, system-scope relaxed flag words (the persistent MNIST step's hand-off form)
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-typedef unsigned __attribute__((address_space(1))) gu32_t;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xrsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ void xst16(const void* base, int off, f32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i_t, v), xrsrc(base), off, 0, 17);
-}
-__device__ __forceinline__ void xst8(const void* base, int off, int a, float b) {
-  __builtin_amdgcn_raw_buffer_store_b64((v2i_t){a, __float_as_int(b)}, xrsrc(base), off, 0, 17);
-}
-__device__ __forceinline__ void xst4(const void* base, int off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), xrsrc(base), off, 0, 17);
-}
-__device__ __forceinline__ f32x4 xld16(const void* base, int off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc(base), off, 0, 17));
-}
-__device__ __forceinline__ v2i_t xld8(const void* base, int off) {
-  return __builtin_amdgcn_raw_buffer_load_b64(xrsrc(base), off, 0, 17);
-}
-__device__ __forceinline__ float xld4(const void* base, int off) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xrsrc(base), off, 0, 17));
-}
+// The cross-rank exchange (DP) uses wg_prims.h's system-scope buffer family (bst* / bld* <SYS>) on the
+// uncached exchange buffers and system-scope relaxed flag words (the persistent MNIST step's hand-off form)
 __device__ __forceinline__ int perm8(int wave) { return (wave + 5) & 7; }
 
 struct Own {
@@ -503,7 +465,7 @@ __device__ __forceinline__ void xpush_dw(int slot, int par, f32x4 acc) {
   const int off = (slot * NT + (int)threadIdx.x) * 16;
   for (int r = 0; r < C.world; ++r) {
     const int sl = C.loopback ? r : C.rank;
-    xst16(C.xbuf[r] + (long)(par * XMAX + sl) * XPAY, off, acc);
+    bst16<SYS>(rsrc(C.xbuf[r] + (long)(par * XMAX + sl) * XPAY), off, acc);
   }
 }
 
@@ -581,10 +543,10 @@ constexpr unsigned SENT = 0xFFFFFFFFu;  // staging sentinel (a NaN no owner writ
 // whose gradient table borrows the activation images)
 __device__ __forceinline__ void ones_columns(bf16_raw* Lb, int B, int tid) {
   if (tid < B) {
-    if (D1 % 16 == 0) Lb[OFF_A1 + tid * SA1 + D1] = f2b(1.f);
-    if (D2 % 16 == 0) Lb[OFF_A2 + tid * SA2 + D2] = f2b(1.f);
-    if (D3 % 16 == 0) Lb[OFF_A3 + tid * SA3 + D3] = f2b(1.f);
-    if (D4 % 16 == 0) Lb[OFF_A4 + tid * SA4 + D4] = f2b(1.f);
+    if (D1 % 16 == 0) Lb[OFF_A1 + tid * SA1 + D1] = f2bf_hw(1.f);
+    if (D2 % 16 == 0) Lb[OFF_A2 + tid * SA2 + D2] = f2bf_hw(1.f);
+    if (D3 % 16 == 0) Lb[OFF_A3 + tid * SA3 + D3] = f2bf_hw(1.f);
+    if (D4 % 16 == 0) Lb[OFF_A4 + tid * SA4 + D4] = f2bf_hw(1.f);
   }
 }
 
@@ -593,7 +555,7 @@ __device__ __forceinline__ void ones_columns(bf16_raw* Lb, int B, int tid) {
 // peer's page, then wave 0 polls the own page until every peer's word has reached `epoch` (wrap-safe),
 // bounded by the wall clock and the sticky error word.  Returns the verdict to the whole workgroup.
 __device__ __forceinline__ bool exchange_step(const Args& A, long long epoch64, int step, unsigned char* lds) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  drain();
   __syncthreads();
   const auto& C = COLD;
   const bool last = step + 1 == C.nsteps;
@@ -603,16 +565,16 @@ __device__ __forceinline__ bool exchange_step(const Args& A, long long epoch64, 
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     if (lane < C.world && lane != C.rank)
-      __hip_atomic_store((gu32_t*)(C.xflag[lane] + (C.loopback ? lane : C.rank)), ep, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
+      xflag_store(C.xflag[lane] + (C.loopback ? lane : C.rank), ep);
     const unsigned* page = C.xflag[C.rank];
     int good = 1;
     const long long t0 = wall_clock64();
     for (unsigned spins = 0;; ++spins) {
       const bool peer = lane < C.world && lane != C.rank;
-      const int ok = !peer || (int)(__hip_atomic_load((gu32_t*)(page + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - ep) >= 0;
+      const int ok = !peer || (int)(xflag_load(page + lane) - ep) >= 0;
       if (__all(ok)) break;
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load((gu32_t*)C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u) {
+      // (flag_load(C.err), spelled out: through the helper hipcc emits a different poll loop)
+      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load((gu32*)C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u) {
         good = 0;
         break;
       }
@@ -623,7 +585,7 @@ __device__ __forceinline__ bool exchange_step(const Args& A, long long epoch64, 
       }
       __builtin_amdgcn_s_sleep(1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain();
     if (lane == 0) *verdict = good;
   }
   __syncthreads();
@@ -661,14 +623,14 @@ __device__ __forceinline__ void load_unit(f32x4 (&v)[XG], const unsigned char* X
       constexpr int S0_ = 2 * U;
       const int S = S0_ + q / 2, r = q % 2;
       const bool on = (q / 2 ? slot_owned<2 * U + 1>(p, wave) : slot_owned<2 * U>(p, wave)) && r < W;
-      v[q] = on ? xld16(X + (long)r * XPAY, (S * NT + tid) * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      v[q] = on ? bld16<SYS>(rsrc(X + (long)r * XPAY), (S * NT + tid) * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
   } else {
     constexpr int S = U / 2, G = U % 2;
     const bool on = slot_owned<S>(p, wave) && G * XG < W;
 #pragma unroll
     for (int r = 0; r < XG; ++r)
-      v[r] = on && G * XG + r < W ? xld16(X + (long)(G * XG + r) * XPAY, (S * NT + tid) * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      v[r] = on && G * XG + r < W ? bld16<SYS>(rsrc(X + (long)(G * XG + r) * XPAY), (S * NT + tid) * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
   }
 }
 template <int S, bool RSQ>
@@ -731,8 +693,8 @@ __device__ __forceinline__ void apply_dp(Own& own, unsigned char* lds, int par, 
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = tid + NT * k;
-      v2i_t q = (v2i_t){-1, 0};
-      if (r < W && e < NE) q = xld8(X + (long)r * XPAY, XW_OFF + e * 8);
+      v2i q = (v2i){-1, 0};
+      if (r < W && e < NE) q = bld8<SYS>(rsrc(X + (long)r * XPAY), XW_OFF + e * 8);
       eid[r][k] = q[0];
       eg[r][k] = __int_as_float(q[1]);
     }
@@ -746,7 +708,7 @@ __device__ __forceinline__ void apply_dp(Own& own, unsigned char* lds, int par, 
     if (C.dbg && tid == 0) C.dbg[28] = wall_clock64();  // (HOPSX_PHASE_DBG: every step overwrites; the last stays)
     if (wave == NW - 1 && lane <= D4) {
       float g = 0.f;
-      for (int r = 0; r < W; ++r) g += xld4(X + (long)r * XPAY, XL4_OFF + lane * 4);
+      for (int r = 0; r < W; ++r) g += bld4<SYS>(rsrc(X + (long)r * XPAY), XL4_OFF + lane * 4);
       own.w4 = RSQ ? adagrad_rsq(own.w4, g * ha.gscale, own.s4, -ha.lr) : adagrad(own.w4, g * ha.gscale, own.s4, ha);
     }
   }
@@ -892,8 +854,8 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
   // the input's ones column (db0); the fp32 bias arrays' constant tail: 1 at OUT makes the forward
   // epilogue write the next layer's ones column, -1e30 beyond makes it write zeros
   if (tid < B) {
-    Lb[OFF_A0 + tid * SA0 + D0] = f2b(1.f);
-    Lb[OFF_A0 + BP * SA0 + tid * SA0 + D0] = f2b(1.f);
+    Lb[OFF_A0 + tid * SA0 + D0] = f2bf_hw(1.f);
+    Lb[OFF_A0 + BP * SA0 + tid * SA0 + D0] = f2bf_hw(1.f);
   }
   if (tid < 16) {
     if (D1 + tid < 16 * L0::OT) LF[F_B0 + D1 + tid] = tid ? -1e30f : 1.f;
@@ -902,7 +864,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
     if (D4 + tid < 16 * L3::OT) LF[F_B3 + D4 + tid] = tid ? -1e30f : 1.f;
   }
   ones_columns(Lb, B, tid);
-  if (evb && eg < D0) Lb[OFF_A0 + eb * SA0 + eg] = f2b(nd);
+  if (evb && eg < D0) Lb[OFF_A0 + eb * SA0 + eg] = f2bf_hw(nd);
   {
     const int p = perm8(wave);
     put_seq<L3, R3>(Lb, LF, p, lane, own.w + S3);
@@ -1082,7 +1044,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
             const auto& C = COLD;
             const int id = ld ? idt[c * BP + b] : -1;
             for (int r = 0; r < C.world; ++r)
-              xst8(C.xbuf[r] + (long)(par * XMAX + (C.loopback ? r : C.rank)) * XPAY, XW_OFF + (c * BP + b) * 8, id, g);
+              bst8<SYS>(rsrc(C.xbuf[r] + (long)(par * XMAX + (C.loopback ? r : C.rank)) * XPAY), XW_OFF + (c * BP + b) * 8, id, g);
           }
         }
       }
@@ -1096,7 +1058,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
         const auto& C = COLD;
         if (lane <= D4)
           for (int r = 0; r < C.world; ++r)
-            xst4(C.xbuf[r] + (long)(par * XMAX + (C.loopback ? r : C.rank)) * XPAY, XL4_OFF + lane * 4, g);
+            bst4<SYS>(rsrc(C.xbuf[r] + (long)(par * XMAX + (C.loopback ? r : C.rank)) * XPAY), XL4_OFF + lane * 4, g);
       } else {
       float s1 = own.s4;
       const float wn = RSQ ? adagrad_rsq(own.w4, g * ha.gscale, s1, -ha.lr) : adagrad(own.w4, g * ha.gscale, s1, ha);
@@ -1167,7 +1129,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
 #pragma unroll
       for (int m = 0; m < 4; ++m) cn[m] = nid[m];
       const float yn = ny;
-      if (!last && evb && eg < D0) Lb[OFF_A0 + ((step + 1) & 1) * BP * SA0 + eb * SA0 + eg] = f2b(nd);
+      if (!last && evb && eg < D0) Lb[OFF_A0 + ((step + 1) & 1) * BP * SA0 + eb * SA0 + eg] = f2bf_hw(nd);
 #pragma unroll
       for (int m = 0; m < 4; ++m)
         if (eg + 4 * m < NWIDE) idt[(eg + 4 * m) * BP + eb] = cn[m];
@@ -1245,7 +1207,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
           for (int k = 0; k < 4 && e + k < span; ++k)
             if (su[e + k] != SENT) {
               dst[e + k] = stage[e + k];
-              if (!pass && C.shadow) C.shadow[C.deep_lo + e + k] = f2b(stage[e + k]);
+              if (!pass && C.shadow) C.shadow[C.deep_lo + e + k] = f2bf_hw(stage[e + k]);
             }
         }
       }
@@ -1274,7 +1236,7 @@ __global__ __launch_bounds__(NT) void taxi_step_k(Args A) {
         wm[r] = w;
         zs[r] = t.x;
         ns[r] = t.y;
-        if (sh) sh[r] = f2b(w);
+        if (sh) sh[r] = f2bf_hw(w);
       }
     }
     if (tid == 0) {

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from ..runtime.capture import graph as _capture_graph
+from ..runtime.launch_slots import ArgSlots
 from torch import nn
 
 from .. import nn as hnn
@@ -209,6 +210,12 @@ class TaxiExchange:
         self._opened, self._owned = [], []
 
 
+def _taxi_step2_store(*args) -> int:
+    from ..ops import _C
+
+    return _C.ext().taxi_step2_store(*args)
+
+
 class FusedWideDeepStep:
     """The whole taxi training step as ONE kernel launch (csrc/ops/widedeep_step.hip): forward,
     sigmoid cross-entropy, backward, FTRL (wide) + Adagrad (deep) updates, step counters and the
@@ -249,7 +256,8 @@ class FusedWideDeepStep:
         self._B = None
         self._v2: dict = {}
         self._zn = None
-        self._v2slots = {}  # cached v2 launch arguments: key -> C++ slot (_v2_slot)
+        # cached v2 launch arguments: key -> C++ slot (_v2_slot)
+        self._v2slots = ArgSlots(_taxi_step2_store)
         dev = self.arena.device
         self.loss = torch.zeros(1, device=dev)
         self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -328,18 +336,19 @@ class FusedWideDeepStep:
         """The C++-side argument slot of this v2 launch shape, built once per key (the data, the step count,
         the hyper-parameters): a run's few launch shapes (warm-up, steps_per_execution, the remainder) each
         get their own, so no argument vector is rebuilt inside a timed loop."""
-        from ..ops import _C
-        from ..ops.functional import rng_state
-
         a = self.arena
         B = dense.shape[-2]
         fl = self._floats()
         key = (dense.data_ptr(), cat.data_ptr(), label.data_ptr(), nbatch, cursor.data_ptr(), nsteps, B,
                tuple(fl), id(a.master), self.dbg is not None, id(self.xdp))
-        slots = self.__dict__.setdefault("_v2slots", {})
-        sid = slots.get(key)
-        if sid is not None:
-            return sid
+        return self._v2slots.get(key, lambda: self._v2_args(dense, cat, label, nbatch, cursor, nsteps, fl))
+
+    def _v2_args(self, dense, cat, label, nbatch: int, cursor, nsteps: int, fl: list):
+        """(ptrs, ints, floats, wide rows) of a v2 launch."""
+        from ..ops.functional import rng_state
+
+        a = self.arena
+        B = dense.shape[-2]
         ptr = lambda t: 0 if t is None else int(t.data_ptr())  # noqa: E731
         rows = int(self.model.wide.weight.shape[0])
         if self._zn is None:
@@ -354,10 +363,7 @@ class FusedWideDeepStep:
                 ptr(self.ftrl.step_count), ptr(rng_state(a.device)), ptr(self.dbg), ptr(self._zn), rsq]
         if self.xdp is not None:
             ptrs += self.xdp.ptrs()
-        free = slots.pop(next(iter(slots))) if len(slots) >= 8 else -1  # reuse the oldest slot id
-        sid = _C.ext().taxi_step2_store(free, ptrs, self._ints(B, nbatch, nsteps), fl, rows)
-        slots[key] = sid
-        return sid
+        return ptrs, self._ints(B, nbatch, nsteps), fl, rows
 
     def _launch(self, dense, cat, label, nbatch: int, cursor, nsteps: int = 1):
         from ..ops import _C

@@ -9,30 +9,19 @@ usage: python tools/persist_isa.py [--src FILE] [--keep-asm OUT.s] [--resources]
 import argparse
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from kernel_asm import compile_asm  # noqa: E402  (the one compile command line)
 
 # the MFMA-carrying segments of one step, in program order (DP: the replica-order fc1 weight gradient follows)
 NAMES = ["conv2 + bias/relu/pool/dropout epilogue", "fc1 partial product", "fc1 dgrad + pool backward",
          "conv2 weight gradient", "publish C part 1 + conv2 dgrad + fc1 wgrad + col2im + conv1 wgrad",
          "fc1 wgrad over the replicas + fc1 Adadelta (DP)"]
-
-
-def compile_asm(src, out, resources=False):
-    from hops_examples_amd import _build
-
-    cmd = [_build.HIPCC, *_build.HIP_FLAGS, *_build._py_includes(), f"-I{os.path.dirname(src)}",
-           "--cuda-device-only", "-S", src, "-o", out]
-    if resources:
-        cmd.append("-Rpass-analysis=kernel-resource-usage")
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        sys.exit("compile failed:\n" + " ".join(cmd) + "\n" + r.stdout)
-    return r.stdout
 
 
 def instructions(body):
