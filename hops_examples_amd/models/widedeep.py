@@ -29,8 +29,6 @@ import os
 import numpy as np
 import torch
 
-from ..runtime.capture import graph as _capture_graph
-from ..runtime.launch_slots import ArgSlots
 from torch import nn
 
 from .. import nn as hnn
@@ -93,446 +91,6 @@ def make_optimizer(model: TaxiWideDeep, ftrl_lr: float = 0.2, adagrad_lr: float 
 
     return optim.Chain(optim.Ftrl(model.wide, lr=min(ftrl_lr, 1.0 / math.sqrt(N_WIDE))),
                        optim.Adagrad(model.deep, lr=adagrad_lr, initial_accumulator_value=0.1))
-
-
-class TaxiExchange:
-    """The cross-rank exchange of the data-parallel v2 taxi step (csrc/ops/taxi_step.hip, DP
-    instantiation): this rank's uncached exchange buffer and flag page, every peer's mapped through IPC
-    handles exchanged over the default process group (ranks on one node; they may share a GPU — the step
-    is one workgroup), the global step counter (exchange epoch base) and a sticky error word.
-
-    Each rank's kernel pushes its dW accumulators and wide-row gradients into every rank's buffer, raises
-    its flag word in every peer's page and sums the W ranks' gradients in rank order before the update:
-    one cross-rank hop per step and bit-identical replicas, the MirroredStrategy global-batch step of the
-    reference's TFX trainer (README.md:99-112) at 2..8 GPUs.  ``loopback=W``: ONE process plays W ranks
-    (the peers' buffers are its own), for tests."""
-
-    def __init__(self, device, world: int | None = None, loopback: int = 0, timeout_s: float | None = None):
-        import torch.distributed as dist
-
-        from ..ops import _C
-        from ..parallel import dist as hdist
-        from ..parallel import oneshot
-
-        self.device = torch.device(device)
-        xb, xf, xmax, self.pay = _C.ext().taxi_step2_xgeom()
-        self.loopback = int(loopback)
-        if self.loopback > 1:
-            self.world, self.rank = self.loopback, 0
-        else:
-            self.world = int(world) if world is not None else hdist.world_size()
-            self.rank = hdist.rank() if self.world > 1 else 0
-        if not 2 <= self.world <= xmax:
-            raise ValueError(f"the data-parallel taxi step takes 2..{xmax} ranks")
-        self.timeout_ms = int(1000 * float(timeout_s or os.environ.get("HOPSX_TAXI_DP_TIMEOUT_S", "60")))
-        C = oneshot.ext()
-        self._owned, self._opened = [], []
-        err = None
-        try:
-            buf, hb = C.alloc(int(xb), True)
-            self._owned.append(buf)
-            flg, hf = C.alloc(int(xf) * 4, True)
-            self._owned.append(flg)
-        except Exception as e:  # every rank must learn of it before the handle exchange
-            err, hb, hf = repr(e), None, None
-        self.xstep = torch.zeros(1, device=self.device, dtype=torch.int64)
-        self.err = torch.zeros(4, device=self.device, dtype=torch.int32)
-        if self.loopback > 1:
-            if err:
-                raise RuntimeError(f"taxi DP exchange setup failed: {err}")
-            self.bufs, self.flags = [buf] * self.world, [flg] * self.world
-            return
-        objs = [None] * self.world
-        dist.all_gather_object(objs, (self.rank, None if err else bytes(hb), None if err else bytes(hf), err))
-        bad = [(o[0], o[3]) for o in objs if o[3]]
-        if bad:
-            self.close()
-            raise RuntimeError(f"taxi DP exchange setup failed on ranks {bad}")
-        self.bufs, self.flags = [0] * self.world, [0] * self.world
-        try:
-            for r, b, f, _ in objs:
-                if r == self.rank:
-                    self.bufs[r], self.flags[r] = buf, flg
-                else:
-                    self.bufs[r] = C.open(b)
-                    self._opened.append(self.bufs[r])
-                    self.flags[r] = C.open(f)
-                    self._opened.append(self.flags[r])
-        except Exception as e:
-            err = repr(e)
-        oks = [None] * self.world
-        dist.all_gather_object(oks, err)
-        if any(oks):
-            self.close()
-            raise RuntimeError(f"taxi DP: mapping a peer's exchange buffer failed: {oks}")
-
-    def ptrs(self) -> list[int]:
-        """The kernel's data-parallel pointer tail (taxi_step.hip hopsx_taxi_step2)."""
-        mode = self.world | (self.rank << 8) | ((1 if self.loopback > 1 else 0) << 16)
-        return [mode, self.timeout_ms, self.err.data_ptr(), self.xstep.data_ptr()] + list(self.bufs) + list(self.flags)
-
-    def sync_replicas(self, arena) -> None:
-        """Collective: every replica starts from rank 0's parameters and optimizer state."""
-        import torch.distributed as dist
-
-        if self.loopback > 1:
-            return
-        gloo = dist.get_backend() == "gloo"  # (rehearsals: ranks sharing a GPU; gloo broadcasts host copies)
-        for t in [arena.master] + [arena.state(k) for k in ("adagrad_s0", "ftrl_s0", "ftrl_s1")]:
-            if gloo:
-                h = t.cpu()
-                dist.broadcast(h, 0)
-                t.copy_(h)
-            else:
-                dist.broadcast(t, 0)
-        if arena.shadow is not None:
-            arena.shadow.copy_(arena.master.to(arena.shadow.dtype))
-        torch.cuda.synchronize(self.device)
-        dist.barrier()
-
-    def check(self) -> None:
-        e = int(self.err[0].item()) & 0xFFFFFFFF
-        if e:
-            raise RuntimeError(f"taxi DP: a peer's gradients did not arrive within {self.timeout_ms} ms "
-                               f"(step {e & 0xFFFFFF} of its launch); the replicas' state is partial")
-
-    def close(self) -> None:
-        if not self._owned:
-            return
-        from ..parallel import oneshot
-
-        C = oneshot.ext()
-        torch.cuda.synchronize(self.device)
-        for q in self._opened:
-            C.close(q)
-        for q in self._owned:
-            C.free(q)
-        self._opened, self._owned = [], []
-
-
-def _taxi_step2_store(*args) -> int:
-    from ..ops import _C
-
-    return _C.ext().taxi_step2_store(*args)
-
-
-class FusedWideDeepStep:
-    """The whole taxi training step as ONE kernel launch (csrc/ops/widedeep_step.hip): forward,
-    sigmoid cross-entropy, backward, FTRL (wide) + Adagrad (deep) updates, step counters and the
-    batch cursor of an HBM-resident epoch — one workgroup holding the model and the batch in LDS.
-
-    Same model, optimizers and results as ``TrainStep(model, make_optimizer(model), "bce_logits")``
-    (fp32 GEMMs instead of bf16).  Data-parallel, two forms: ``xdp`` (a :class:`TaxiExchange`) runs the
-    v2 kernel's data-parallel instantiation — the replicas exchange gradients inside the launch and
-    update in registers, "fused-v2-dp"; ``dp`` (a DataParallel engine): the v1 kernel stops at the
-    gradients, which are all-reduced and applied by the regular optimizer kernels.  ``ok()`` says whether
-    the model/batch fit one workgroup's LDS; otherwise use TrainStep."""
-
-    def __init__(self, model: TaxiWideDeep, optimizer, dp=None, xdp: "TaxiExchange | None" = None):
-        from ..runtime.arena import ParamArena  # noqa: F401 (the model must live in an arena)
-
-        self.model, self.opt, self.dp, self.xdp = model, optimizer, dp, xdp
-        if dp is not None and xdp is not None:
-            raise ValueError("dp (v1 + all-reduce) and xdp (in-kernel exchange) are exclusive")
-        self.arena = model.wide.weight._hx_arena
-        self.ftrl, self.ada = optimizer.opts
-        lins = [m for m in model.deep if isinstance(m, hnn.Linear)]
-        self.lins = lins
-        self.dims = [lins[0].weight.shape[1]] + [m.weight.shape[0] for m in lins]
-        self.acts_ok = (all(m.activation == "relu" for m in lins[:-1]) and lins[-1].activation is None
-                        and all(m.bias is not None for m in lins))
-        if dp is not None:
-            optimizer.grad_scale = dp.grad_scale()
-        self._graph = None
-        self._key = None
-        self._graphU = None
-        self._keyU = None
-        self._graphR: dict = {}  # remainder graphs (Keras steps_per_execution tail): U -> graph
-        # steps per replayed graph; on one GPU they run inside ONE launch (widedeep_step.hip nsteps)
-        self.steps_per_execution = max(1, int(os.environ.get("HOPSX_TAXI_STEPS_PER_EXEC",
-                                                             os.environ.get("HOPSX_STEPS_PER_EXEC", "32"))))
-        self._slot_cache = {}
-        self._n = 0
-        self._B = None
-        self._v2: dict = {}
-        self._zn = None
-        # cached v2 launch arguments: key -> C++ slot (_v2_slot)
-        self._v2slots = ArgSlots(_taxi_step2_store)
-        dev = self.arena.device
-        self.loss = torch.zeros(1, device=dev)
-        self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.cursor = torch.zeros(1, device=dev, dtype=torch.int64)
-        # HOPSX_PHASE_DBG=1: the kernel stamps its phase boundaries here (tools/taxi_phases.py)
-        self.dbg = (torch.zeros(32, device=dev, dtype=torch.int64)
-                    if os.environ.get("HOPSX_PHASE_DBG") == "1" else None)
-
-    def _ints(self, B: int, nbatch: int, nsteps: int = 1) -> list[int]:
-        L = len(self.lins)
-        iv = ([L, B, nbatch, N_WIDE, int(self.model.wide.weight._hx_off), int(self.dp is None), 2] + self.dims
-              + [int(m.weight._hx_off) for m in self.lins] + [int(m.bias._hx_off) for m in self.lins])
-        return iv + [int(nsteps)] if nsteps > 1 else iv
-
-    def ok(self, B: int) -> bool:
-        from ..ops import _C
-
-        dev = self.arena.device
-        if self.xdp is not None:  # the in-kernel exchange exists in the v2 kernel only
-            return dev.type == "cuda" and self.v2(B)
-        return (dev.type == "cuda" and self.acts_ok and self.dims[-1] == 1
-                and (self.v2(B) or _C.ext().widedeep_step_lds(self._ints(B, 1)) > 0))
-
-    def check(self) -> None:
-        """Raise if the data-parallel exchange of any launch failed (sticky device error word)."""
-        if self.xdp is not None:
-            self.xdp.check()
-
-    def digest(self) -> tuple[float, int]:
-        """(sum, integer bit-sum) of the fp32 arena: equal on every replica iff the replicas agree."""
-        m = self.arena.master
-        return float(m.double().sum()), int(m.view(torch.int32).long().sum())
-
-    def v2(self, B: int) -> bool:
-        """The v2 kernel (csrc/ops/taxi_step.hip: bf16 MFMA, wide table + optimizer state on chip) takes
-        the default taxi shape on one GPU; HOPSX_TAXI_KERNEL=v1 forces the fp32 v1 kernel."""
-        from ..ops import _C
-
-        key = (B, self.dp is None, os.environ.get("HOPSX_TAXI_KERNEL", "v2"), self.xdp is not None)
-        r = self._v2.get(key)
-        if r is None:
-            r = (self.dp is None and key[2] != "v1" and self.acts_ok and self.arena.device.type == "cuda"
-                 and _C.ext().taxi_step2_ok(self._ints(B, 1), int(self.model.wide.weight.shape[0])) > 0)
-            self._v2[key] = r
-        return r
-
-    @property
-    def kernel(self) -> str:
-        k = "v2" if self.v2(self._B or TRAIN_BATCH_SIZE) else "v1"
-        return k + "-dp" if self.xdp is not None and k == "v2" else k
-
-    def _slots(self, B: int):
-        """Host-built table: LDS slot of every deep arena element for batch size B (cached)."""
-        from ..ops import _C
-        from ..ops.kernels import check
-
-        t = self._slot_cache.get(B)
-        if t is None:
-            lo = int(self.lins[0].weight._hx_off)
-            hi = int(self.lins[-1].bias._hx_off) + self.dims[-1]
-            host = torch.empty(hi - lo, dtype=torch.int32)
-            check(_C.ext().widedeep_slots(self._ints(B, 1), host.data_ptr(), hi - lo), "widedeep_slots")
-            t = host.to(self.arena.device)
-            self._slot_cache[B] = t
-        return t
-
-    def _floats(self) -> list[float]:
-        def pad8(v):
-            return [float(x) for x in v] + [0.0] * (8 - len(v))
-
-        self.ada.lr = self.ada.param_groups[0]["lr"]
-        self.ftrl.lr = self.ftrl.param_groups[0]["lr"]
-        return pad8(self.ada._hp()) + pad8(self.ftrl._hp())
-
-    def _v2_slot(self, dense, cat, label, nbatch: int, cursor, nsteps: int) -> int:
-        """The C++-side argument slot of this v2 launch shape, built once per key (the data, the step count,
-        the hyper-parameters): a run's few launch shapes (warm-up, steps_per_execution, the remainder) each
-        get their own, so no argument vector is rebuilt inside a timed loop."""
-        a = self.arena
-        B = dense.shape[-2]
-        fl = self._floats()
-        key = (dense.data_ptr(), cat.data_ptr(), label.data_ptr(), nbatch, cursor.data_ptr(), nsteps, B,
-               tuple(fl), id(a.master), self.dbg is not None, id(self.xdp))
-        return self._v2slots.get(key, lambda: self._v2_args(dense, cat, label, nbatch, cursor, nsteps, fl))
-
-    def _v2_args(self, dense, cat, label, nbatch: int, cursor, nsteps: int, fl: list):
-        """(ptrs, ints, floats, wide rows) of a v2 launch."""
-        from ..ops.functional import rng_state
-
-        a = self.arena
-        B = dense.shape[-2]
-        ptr = lambda t: 0 if t is None else int(t.data_ptr())  # noqa: E731
-        rows = int(self.model.wide.weight.shape[0])
-        if self._zn is None:
-            self._zn = torch.empty(rows, 2, device=a.device)  # the kernel's (z, n) scratch
-        # Adagrad as w -= lr g rsq(s) (one transcendental): exact to fp32 when wd == 0 and eps is
-        # below the resolution of sqrt(s), whose floor is the initial accumulator
-        floor = float(getattr(self.ada, "initial_accumulator_value", 0.0))
-        rsq = int(self.ada.weight_decay == 0 and floor > 0 and self.ada.hp["eps"] < 1e-7 * math.sqrt(floor))
-        ptrs = [ptr(a.master), ptr(a.grad), ptr(a.shadow), ptr(a.state("adagrad_s0")),
-                ptr(a.state("ftrl_s0")), ptr(a.state("ftrl_s1")), ptr(dense), ptr(cat), ptr(label),
-                ptr(cursor), ptr(self.loss), ptr(self.correct), ptr(self.ada.step_count),
-                ptr(self.ftrl.step_count), ptr(rng_state(a.device)), ptr(self.dbg), ptr(self._zn), rsq]
-        if self.xdp is not None:
-            ptrs += self.xdp.ptrs()
-        return ptrs, self._ints(B, nbatch, nsteps), fl, rows
-
-    def _launch(self, dense, cat, label, nbatch: int, cursor, nsteps: int = 1):
-        from ..ops import _C
-        from ..ops.functional import rng_state
-        from ..ops.kernels import check, stream
-
-        a = self.arena
-        B = dense.shape[-2]
-        self._B = B
-        if self.v2(B):
-            check(_C.ext().taxi_step2_slot(self._v2_slot(dense, cat, label, nbatch, cursor, nsteps), stream()),
-                  "taxi_step2")
-            return
-        ptr = lambda t: 0 if t is None else int(t.data_ptr())  # noqa: E731
-        ptrs = [ptr(a.master), ptr(a.grad), ptr(a.shadow), ptr(a.state("adagrad_s0")), ptr(a.state("ftrl_s0")),
-                ptr(a.state("ftrl_s1")), ptr(dense), ptr(cat), ptr(label), ptr(cursor), ptr(self.loss),
-                ptr(self.correct), ptr(self.ada.step_count), ptr(self.ftrl.step_count), ptr(rng_state(a.device)),
-                ptr(self.dbg)]
-        ptrs.append(ptr(self._slots(B)))
-        check(_C.ext().widedeep_step(ptrs, self._ints(B, nbatch, nsteps), self._floats(), stream()),
-              "widedeep_step")
-
-    def _finish(self):
-        if self.dp is not None:
-            self.dp.allreduce_all()
-            self.opt.step()
-            if hasattr(self.dp, "post_step"):
-                self.dp.post_step()
-
-    def __call__(self, x, y):
-        """One step on an explicit batch: x = (dense [B, 3], cat [B, 13] int64), y [B, 1]."""
-        from ..runtime import health
-
-        self._n += 1
-        health.beat(self._n)
-        dense, cat = x
-        self._launch(dense.float().contiguous(), cat.contiguous(), y.float().contiguous(), 1, None)
-        self._finish()
-        return {"loss": self.loss, "correct": self.correct, "count": dense.shape[0]}
-
-    def step_resident(self, xs, ys, graph: bool = True):
-        """One step on batch ``cursor`` of a resident epoch xs = (dense [nb, B, 3] fp32, cat [nb, B, 13]),
-        ys [nb, B, 1]; the kernel advances the cursor.  Single-GPU steps replay a captured graph."""
-        from ..runtime import health
-
-        self._n += 1
-        health.beat(self._n)
-        dense, cat = xs
-        key = (dense.data_ptr(), cat.data_ptr(), ys.data_ptr(), tuple(self._floats()))
-        if not graph or not self._graphable():
-            self._launch(dense, cat, ys, dense.shape[0], self.cursor)
-            self._finish()
-        else:
-            if self._key != key:  # new data or hyper-parameters (e.g. an lr schedule): recapture
-                if not self.v2(dense.shape[-2]):
-                    self._slots(dense.shape[-2])  # host->device copy of the slot table must precede capture
-                self._sync_hp()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with _capture_graph(g):
-                    self._launch(dense, cat, ys, dense.shape[0], self.cursor)
-                    self._finish()  # multi-rank: the P2P all-reduce + optimizers are graph nodes too
-                self._graph, self._key = g, key
-                # capture does not execute: run this step through the graph
-            self._graph.replay()
-            if self.dp is not None:
-                self.dp.poll()
-        return {"loss": self.loss, "correct": self.correct, "count": dense.shape[1]}
-
-    def _direct(self, dense) -> bool:
-        """Single-GPU v2 step with its in-kernel step loop: launched directly (``HOPSX_TAXI_DIRECT=0``
-        keeps the graph replays)."""
-        return (self.dp is None and self.arena.device.type == "cuda" and self.v2(dense.shape[-2])
-                and os.environ.get("HOPSX_TAXI_INKERNEL_LOOP", "1") == "1"
-                and os.environ.get("HOPSX_TAXI_DIRECT", "1") == "1")
-
-    def _graphable(self) -> bool:
-        """One GPU, or a data-parallel engine whose collectives are graph-capturable (P2P kernels)."""
-        return self.arena.device.type == "cuda" and (
-            self.dp is None or getattr(self.dp, "capturable", lambda: False)())
-
-    def _sync_hp(self):
-        if self.dp is not None and hasattr(self.opt, "sync_hp"):
-            self.opt.sync_hp()
-
-    def _capture_u(self, dense, cat, ys, U: int):
-        """U consecutive steps in one graph: ONE launch running U steps in-kernel on one GPU (the
-        weights stay on chip between them); U launches + gradient exchanges when data-parallel."""
-        if not self.v2(dense.shape[-2]):
-            self._slots(dense.shape[-2])
-        self._sync_hp()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with _capture_graph(g):
-            if self.dp is None and os.environ.get("HOPSX_TAXI_INKERNEL_LOOP", "1") == "1":
-                self._launch(dense, cat, ys, dense.shape[0], self.cursor, nsteps=U)
-            else:
-                for _ in range(U):
-                    self._launch(dense, cat, ys, dense.shape[0], self.cursor)
-                    self._finish()
-        return g
-
-    def prepare_resident(self, xs, ys, n: int | None = None) -> None:
-        """Capture (not run) the U-step graph for this resident epoch, so it is built before a timed
-        loop; with ``n`` also the graph of the remainder n % U (Keras steps_per_execution tail)."""
-        dense, cat = xs
-        U = self.steps_per_execution
-        if n and self._direct(dense) and self.v2(dense.shape[-2]):
-            # direct launches (run_resident): their argument slots for the launch shapes of n steps
-            for k in {min(int(n), U), int(n) % U} - {0}:
-                self._v2_slot(dense, cat, ys, dense.shape[0], self.cursor, k)
-            return
-        if U <= 1 or not self._graphable() or self._graph is None:
-            return
-        key = (dense.data_ptr(), cat.data_ptr(), ys.data_ptr(), tuple(self._floats()), U)
-        if self._keyU != key:
-            self._graphU, self._keyU = self._capture_u(dense, cat, ys, U), key
-            self._graphR = {}
-        rem = (n or 0) % U
-        if rem > 1 and rem not in self._graphR:
-            self._graphR[rem] = self._capture_u(dense, cat, ys, rem)
-
-    def run_resident(self, xs, ys, n: int, graph: bool = True):
-        """``n`` consecutive resident steps; single-GPU graph steps are replayed ``steps_per_execution``
-        launches per graph (Keras steps_per_execution; each launch is a whole step on the next batch,
-        the kernel advances the device cursor), so the per-replay gap is paid once per U steps."""
-        from ..runtime import health
-
-        U = self.steps_per_execution
-        dense, cat = xs
-        r = None
-        if graph and self._direct(dense):
-            # one GPU, whole steps in one kernel: each launch runs up to U steps in-kernel, launched
-            # directly (a one-node graph replay costs more host time than the launch it replaces) with
-            # the argument vectors kept in a C++ slot
-            while n > 0:
-                k = min(n, U)
-                health.beat_range(self._n + 1, k)
-                self._n += k
-                self._launch(dense, cat, ys, dense.shape[0], self.cursor, nsteps=k)
-                n -= k
-            return {"loss": self.loss, "correct": self.correct, "count": dense.shape[1]}
-        while n > 0:
-            usable = U > 1 and graph and self._graphable() and self._graph is not None
-            if usable and n < U and n in self._graphR:
-                self.prepare_resident(xs, ys)  # (re-keys on new data / hyper-parameters)
-                g = self._graphR.get(n)
-                if g is not None:
-                    health.beat_range(self._n + 1, n)
-                    self._n += n
-                    g.replay()
-                    if self.dp is not None:
-                        self.dp.poll()
-                    n = 0
-                    r = {"loss": self.loss, "correct": self.correct, "count": dense.shape[1]}
-                    continue
-            if n < U or not usable:
-                r = self.step_resident(xs, ys, graph=graph)
-                n -= 1
-                continue
-            self.prepare_resident(xs, ys)
-            health.beat_range(self._n + 1, U)
-            self._n += U
-            self._graphU.replay()
-            if self.dp is not None:
-                self.dp.poll()
-            n -= U
-            r = {"loss": self.loss, "correct": self.correct, "count": dense.shape[1]}
-        return r
 
 
 def reference_steps(W, b, w4, b4, wide, ada_s, ftrl_z, ftrl_n, hp_ada, hp_ftrl, dense, cat, label, steps):
@@ -653,6 +211,7 @@ def bench_taxi(dev, batch: int, steps: int, warmup: int, timed, world: int = 1, 
     from ..parallel.dp import DataParallel
     from ..runtime.arena import ParamArena
     from ..runtime.step import TrainStep
+    from ..runtime.taxi_step import FusedWideDeepStep, TaxiExchange
 
     model = TaxiWideDeep().to(dev)
     ParamArena.from_module(model, dev)
@@ -718,12 +277,8 @@ def bench_taxi(dev, batch: int, steps: int, warmup: int, timed, world: int = 1, 
     loss = float(out["r"]["loss"].reshape(-1)[0])
     replicas = None
     if xdp is not None:
-        import torch.distributed as dist
-
         fused.check()  # the exchange's sticky error word (outside the timed region)
-        digs = [None] * world
-        dist.all_gather_object(digs, fused.digest())
-        replicas = all(d == digs[0] for d in digs)
+        replicas = xdp.replicas_agree(fused.digest())
         xdp.close()
     return {"steps_per_sec": round(steps / el, 1), "examples_per_sec": round(batch * world * steps / el, 1),
             "ms_per_step": round(el / steps * 1e3, 4), "batch_per_gpu": batch, "loss": round(loss, 4),

@@ -10,6 +10,12 @@ from __future__ import annotations
 from typing import Callable, Hashable, Optional
 
 
+def launch_shapes(n: int, per_launch: int) -> set:
+    """The step counts of the launches that run ``n`` steps at ``per_launch`` steps a launch: the full
+    launch (or ``n`` itself when smaller) and the remainder."""
+    return {min(n, per_launch), n % per_launch} - {0}
+
+
 class ArgSlots:
     """key -> slot id of ``store``.  ``store(slot, *args) -> slot`` writes an argument set into ``slot``, or
     into a new slot when ``slot`` is -1."""

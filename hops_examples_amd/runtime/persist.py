@@ -36,7 +36,7 @@ import os
 
 import torch
 
-from .launch_slots import ArgSlots
+from .launch_slots import ArgSlots, launch_shapes
 
 _GEOM = None
 
@@ -197,8 +197,7 @@ class PersistentMnistStep:
         default_t = "60" if self.world > 1 else "2"
         self.timeout_ms = int(1000 * float(timeout_s or os.environ.get("HOPSX_PERSIST_TIMEOUT_S", default_t)))
         self._xptrs: list[int] = []
-        self._owned: list[int] = []
-        self._opened: list[int] = []
+        self._px = None  # the real cross-rank exchange (PeerExchange), when there is one
         self.exchange = exchange
         self.selftest_report: dict | None = None
         if exchange is not None:
@@ -217,55 +216,18 @@ class PersistentMnistStep:
 
     # ------------------------------------------------------------------ data parallel
     def _setup_exchange(self) -> None:
-        """Allocate this rank's uncached exchange buffer + flag page, map every peer's (IPC handles
-        through the default process group), make the replicas identical (rank 0's weights)."""
+        """This rank's exchange buffer + flag page and every peer's (``PeerExchange``: IPC handles through
+        the default process group); then make the replicas identical (rank 0's weights)."""
         import torch.distributed as dist
 
-        from ..parallel import oneshot
+        from .peer_exchange import PeerExchange
 
-        C = oneshot.ext()
         g = self.geom
         local = self.loopback > 1
-        err = None
-        from ..parallel import dist as hdist
-
-        hdist.register(self)  # ordered teardown (close: local) at shutdown / interpreter exit
-        try:
-            buf, hb = C.alloc(int(g["x_bytes"]), True)
-            self._owned.append(buf)
-            flg, hf = C.alloc(int(g["xflag_words"]) * 4, True)
-            self._owned.append(flg)
-        except Exception as e:  # every rank must learn of it before the handle exchange
-            err, hb, hf = repr(e), None, None
+        self._px = PeerExchange(self.device, g["x_bytes"], g["xflag_words"], self.world, self.rank, loopback=local,
+                                name="persistent")
         self.xstep = torch.zeros(1, device=self.device, dtype=torch.int64)
-        if local:
-            if err:
-                raise RuntimeError(f"persistent DP exchange setup failed: {err}")
-            bufs, flags = [buf] * self.world, [flg] * self.world
-        else:
-            objs = [None] * self.world
-            dist.all_gather_object(objs, (self.rank, None if err else bytes(hb), None if err else bytes(hf), err))
-            bad = [(o[0], o[3]) for o in objs if o[3]]
-            if bad:
-                self.close()
-                raise RuntimeError(f"persistent DP exchange setup failed on ranks {bad}")
-            bufs, flags = [0] * self.world, [0] * self.world
-            try:
-                for r, b, f, _ in objs:
-                    if r == self.rank:
-                        bufs[r], flags[r] = buf, flg
-                    else:
-                        bufs[r] = C.open(b)
-                        self._opened.append(bufs[r])
-                        flags[r] = C.open(f)
-                        self._opened.append(flags[r])
-            except Exception as e:
-                err = repr(e)
-            oks = [None] * self.world
-            dist.all_gather_object(oks, err)
-            if any(oks):
-                self.close()
-                raise RuntimeError(f"persistent DP: mapping a peer's exchange buffer failed: {oks}")
+        if not local:
             # replicas start from rank 0's parameters and optimizer state
             a = self.arena
             for t in (a.master, self.s1, self.s2):
@@ -274,22 +236,15 @@ class PersistentMnistStep:
             dist.broadcast(self.opt.step_count, 0)
             torch.cuda.synchronize(self.device)
             dist.barrier()
-        self._xptrs = [self.xstep.data_ptr()] + bufs + flags
+        self._xptrs = [self.xstep.data_ptr()] + self._px.bufs + self._px.flags
 
     def close(self) -> None:
         """Unmap the peers' buffers and free this rank's (collective in spirit: call on every rank
         after the last launch has finished)."""
-        if not self._owned:
+        if self._px is None:
             return
-        from ..parallel import oneshot
-
-        C = oneshot.ext()
-        torch.cuda.synchronize(self.device)
-        for p in self._opened:
-            C.close(p)
-        for p in self._owned:
-            C.free(p)
-        self._opened, self._owned, self._xptrs = [], [], []
+        self._px.close()
+        self._px, self._xptrs = None, []
 
     def param_digest(self) -> tuple[float, int]:
         """(sum, integer bit-sum) of the fp32 master: equal on every replica iff the replicas agree."""
@@ -565,7 +520,7 @@ class PersistentMnistStep:
         if n:
             self.opt.sync_hp()
             hp = [float(v) for v in self.opt._hp()]
-            for k in {min(int(n), self.spl), int(n) % self.spl} - {0}:
+            for k in launch_shapes(int(n), self.spl):
                 self._arg_slot(xs, ys, nb, k, hp, self._launch_state(k, hp))
 
     def losses(self, k: int) -> torch.Tensor:

@@ -10,7 +10,7 @@ StatisticsGen      feature statistics of the train split (``featurestore.statist
 SchemaGen          types, value domains and required-ness inferred from the statistics
 Transform          analyze on train, apply to both splits (:mod:`.transform`; transform.hip) ->
                    ``transform/transform_fn.json`` + ``transformed/{train,eval}.parquet``
-Trainer            wide&deep trainer (``models.widedeep``: the whole step in one kernel) fed by the
+Trainer            wide&deep trainer (``runtime.taxi_step``: the whole step in one kernel) fed by the
                    transformed Parquet streamed into HBM (``io.parquet``) -> ``trainer/model.pt``
 Evaluator          accuracy / AUC / log-loss on the eval split, overall and per slice of a feature (TFMA's
                    model analysis; ``runtime.taxi_eval``: the whole split in one launch on the GPU);
@@ -135,9 +135,10 @@ def trainer(root, steps: int = 2000, batch: int = 40, device=None, eval_every: i
     those of ``eval_every=0``."""
     import torch
 
-    from ..models.widedeep import FusedWideDeepStep, TaxiWideDeep, make_optimizer
+    from ..models.widedeep import TaxiWideDeep, make_optimizer
     from ..runtime.arena import ParamArena
     from ..runtime.step import TrainStep
+    from ..runtime.taxi_step import FusedWideDeepStep
 
     root = Path(root)
     dev = torch.device(device) if device is not None else (

@@ -1,6 +1,8 @@
 """runtime/launch_slots.py ArgSlots — the key -> argument-slot cache of the whole-step launches — against a
 fake store that hands out consecutive ids (what the extension's <name>_store does for slot -1)."""
-from hops_examples_amd.runtime.launch_slots import ArgSlots
+import pytest
+
+from hops_examples_amd.runtime.launch_slots import ArgSlots, launch_shapes
 
 
 class FakeStore:
@@ -49,3 +51,9 @@ def test_capacity_is_a_parameter_and_on_evict_optional():
     s = ArgSlots(store, capacity=2)
     assert [s.get(k, lambda: ()) for k in "abc"] == [0, 1, 0] and len(s) == 2
     assert s.get("b", _no_build) == 1
+
+
+@pytest.mark.parametrize("n,U,want", [(20, 8, {8, 4}), (8, 8, {8}), (3, 8, {3}), (16, 8, {8}), (0, 8, set())])
+def test_launch_shapes(n, U, want):
+    """n steps at U per launch: the full launch (or n, when smaller) and the remainder, never 0."""
+    assert launch_shapes(n, U) == want

@@ -1,4 +1,4 @@
-"""The data-parallel instantiation of the v2 taxi step (csrc/ops/taxi_step.hip DP, models/widedeep.py
+"""The data-parallel instantiation of the v2 taxi step (csrc/ops/taxi_step.hip DP, runtime/taxi_step.py
 TaxiExchange): each rank trains on its own batch, the dW accumulators and wide-row gradients are pushed
 to every rank inside the launch and summed in rank order before the in-register Adagrad / FTRL updates.
 
@@ -22,6 +22,7 @@ if not torch.cuda.is_available():  # pragma: no cover
 
 from hops_examples_amd.models import widedeep as WD  # noqa: E402
 from hops_examples_amd.runtime.arena import ParamArena  # noqa: E402
+from hops_examples_amd.runtime.taxi_step import FusedWideDeepStep, TaxiExchange  # noqa: E402
 
 dev = torch.device("cuda", 0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,8 +38,8 @@ def _run(loopback, steps=12, spe=4, B=40, nb=4, seed=1):
     m = m.to(dev)
     ParamArena.from_module(m, dev)
     opt = WD.make_optimizer(m)
-    xdp = WD.TaxiExchange(dev, loopback=loopback, timeout_s=5) if loopback > 1 else None
-    fs = WD.FusedWideDeepStep(m, opt, xdp=xdp)
+    xdp = TaxiExchange(dev, loopback=loopback, timeout_s=5) if loopback > 1 else None
+    fs = FusedWideDeepStep(m, opt, xdp=xdp)
     assert fs.kernel == ("v2-dp" if xdp else "v2")
     fs.steps_per_execution = spe
     fs.run_resident((dense.to(dev), cat.to(dev)), label.to(dev), steps)
@@ -109,7 +110,7 @@ def test_processes_match_fp64_global_batch(world, tmp_path):
     torch.manual_seed(1)
     mm = WD.TaxiWideDeep().to(dev)
     ParamArena.from_module(mm, dev)
-    fs = WD.FusedWideDeepStep(mm, WD.make_optimizer(mm))
+    fs = FusedWideDeepStep(mm, WD.make_optimizer(mm))
     mm.wide.weight._hx_arena.master.copy_(rs[0]["final"]["master"].to(dev))
     got = WD.reference_state(mm, fs)
     names = [f"W{l}" for l in range(4)] + [f"b{l}" for l in range(4)] + ["w4", "wide"]

@@ -23,6 +23,7 @@ from hops_examples_amd.ops import kernels as K  # noqa: E402
 from hops_examples_amd.runtime import capture  # noqa: E402
 from hops_examples_amd.runtime import taxi_eval as TE  # noqa: E402
 from hops_examples_amd.runtime.arena import ParamArena  # noqa: E402
+from hops_examples_amd.runtime.taxi_step import FusedWideDeepStep  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 N = 2085
@@ -228,7 +229,7 @@ def test_live_weights_after_the_training_kernel(ctx):
     and no stale copy of any weight (fp32 master or bf16 shadow)."""
     m, _ = _model(seed=2)
     opt = WD.make_optimizer(m)
-    fused = WD.FusedWideDeepStep(m, opt)
+    fused = FusedWideDeepStep(m, opt)
     assert fused.ok(40)
     td, tc, ty = (t.to(DEV) for t in WD.synth_taxi(8 * 40, seed=4))
     xs, ys = (td.view(8, 40, -1), tc.view(8, 40, -1)), ty.view(8, 40, 1)

@@ -13,6 +13,7 @@ if not torch.cuda.is_available():  # pragma: no cover
 from hops_examples_amd.models import widedeep as WD  # noqa: E402
 from hops_examples_amd.runtime.arena import ParamArena  # noqa: E402
 from hops_examples_amd.runtime.step import TrainStep  # noqa: E402
+from hops_examples_amd.runtime.taxi_step import FusedWideDeepStep  # noqa: E402
 
 dev = torch.device("cuda", 0)
 
@@ -34,7 +35,7 @@ def _setup(B, nb, seed):
     g = g.to(dev)
     ParamArena.from_module(g, dev)
     opt = WD.make_optimizer(g)
-    fs = WD.FusedWideDeepStep(g, opt)
+    fs = FusedWideDeepStep(g, opt)
     return dense, cat, label, g, opt, fs
 
 
@@ -122,7 +123,7 @@ def test_taxi_v2_multi_step_launch_matches_single_launches():
             fs.prepare_resident(xs, ys, n - 1)
             fs.run_resident(xs, ys, n - 1)
             # direct launches: prepare_resident built the launch-argument slot; graph replays: the U-step graph
-            assert len(fs._v2slots) >= 2 if fs._direct(xs[0]) else fs._graphU is not None
+            assert len(fs._v2slots) >= 2 if fs._direct(xs[0]) else fs.steps_per_execution in fs._graphs
         else:
             for _ in range(n):
                 fs.step_resident(xs, ys)
@@ -138,11 +139,79 @@ def test_taxi_v2_multi_step_launch_matches_single_launches():
 def test_taxi_v2_declines_other_shapes(monkeypatch):
     g = WD.TaxiWideDeep(hidden=[64, 32]).to(dev)
     ParamArena.from_module(g, dev)
-    fs = WD.FusedWideDeepStep(g, WD.make_optimizer(g))
+    fs = FusedWideDeepStep(g, WD.make_optimizer(g))
     assert not fs.v2(40) and fs.ok(40)  # the v1 kernel takes it
     g = WD.TaxiWideDeep().to(dev)
     ParamArena.from_module(g, dev)
-    fs = WD.FusedWideDeepStep(g, WD.make_optimizer(g))
+    fs = FusedWideDeepStep(g, WD.make_optimizer(g))
     assert fs.v2(40) and not fs.v2(49)
     monkeypatch.setenv("HOPSX_TAXI_KERNEL", "v1")
     assert not fs.v2(40) and fs.kernel == "v1"
+
+
+def _drive(seed, graph, calls):
+    """A fresh engine from ``_setup(13, 4, seed)`` driven through ``calls(fs, dense, cat, label)``; returns the
+    engine and (cursor, loss, master, adagrad_s0, ftrl_s0, ftrl_s1) after a synchronize."""
+    dense, cat, label, g, opt, fs = _setup(13, 4, seed)
+    calls(fs, dense.to(dev), cat.to(dev), label.to(dev), graph)
+    torch.cuda.synchronize()
+    a = g._hx_arena
+    return fs, [fs.cursor.clone(), fs.loss.clone(), a.master.clone(), a.state("adagrad_s0").clone(),
+                a.state("ftrl_s0").clone(), a.state("ftrl_s1").clone()]
+
+
+def test_taxi_v2_epoch_view_with_the_same_pointer_replays_nothing_stale():
+    """Three graph steps on an epoch of 4 batches, then three on a view of its first 2 (same data_ptr, smaller
+    nbatch): the cursor must wrap at 2, so the graph captured for nbatch = 4 must not be replayed.  Bit-equal to
+    the same calls without graphs (the v2 kernel's sums have a fixed order)."""
+    def calls(fs, dense, cat, label, graph):
+        for _ in range(3):
+            fs.step_resident((dense, cat), label, graph=graph)
+        for _ in range(3):
+            fs.step_resident((dense[:2], cat[:2]), label[:2], graph=graph)
+
+    _, got = _drive(7, True, calls)
+    _, want = _drive(7, False, calls)
+    print("cursor", int(got[0]), int(want[0]), "loss", float(got[1]), float(want[1]))
+    for x, y in zip(got, want):
+        assert torch.equal(x, y)
+
+
+def test_taxi_v2_kernel_choice_is_part_of_the_graph_key(monkeypatch):
+    """HOPSX_TAXI_KERNEL=v1 after a captured v2 step: the next step_resident runs the v1 kernel, not the v2
+    graph.  v1 adds the wide gradients with float atomics: the master to the v1 test's tolerance."""
+    def calls(fs, dense, cat, label, graph):
+        fs.step_resident((dense, cat), label, graph=graph)
+        assert fs.kernel == "v2"
+        monkeypatch.setenv("HOPSX_TAXI_KERNEL", "v1")
+        fs.step_resident((dense, cat), label, graph=graph)
+        assert fs.kernel == "v1"
+        monkeypatch.delenv("HOPSX_TAXI_KERNEL")
+
+    _, got = _drive(8, True, calls)
+    _, want = _drive(8, False, calls)
+    assert torch.equal(got[0], want[0]) and int(got[0]) == 2
+    torch.testing.assert_close(got[1], want[1], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(got[2], want[2], rtol=1e-3, atol=1e-5)
+
+
+def test_taxi_v2_direct_path_launch_sizes():
+    """run_resident on the direct path: n steps at U per launch are launches of U, U, ..., n % U, in that order."""
+    dense, cat, label, g, opt, fs = _setup(13, 4, 9)
+    xs, ys = (dense.to(dev), cat.to(dev)), label.to(dev)
+    if not fs._direct(xs[0]):
+        pytest.skip("the direct launch path is switched off (HOPSX_TAXI_DIRECT / HOPSX_TAXI_INKERNEL_LOOP)")
+    sizes, launch = [], fs._launch
+
+    def recording(dense, cat, label, nsteps=1):
+        sizes.append(nsteps)
+        launch(dense, cat, label, nsteps)
+
+    fs._launch = recording
+    fs.steps_per_execution = 8
+    fs.run_resident(xs, ys, 20)
+    assert sizes == [8, 8, 4]
+    fs.run_resident(xs, ys, 3)
+    assert sizes == [8, 8, 4, 3]
+    torch.cuda.synchronize()
+    assert int(fs.cursor.item()) == 23 % 4

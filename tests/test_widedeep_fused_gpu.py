@@ -16,6 +16,7 @@ if not torch.cuda.is_available():  # pragma: no cover
 from hops_examples_amd.models import widedeep as WD  # noqa: E402
 from hops_examples_amd.runtime.arena import ParamArena  # noqa: E402
 from hops_examples_amd.runtime.step import TrainStep  # noqa: E402
+from hops_examples_amd.runtime.taxi_step import FusedWideDeepStep  # noqa: E402
 
 dev = torch.device("cuda", 0)
 
@@ -48,7 +49,7 @@ def test_fused_widedeep_step_matches_fp32_reference(B, graph):
     g = g.to(dev)
     ParamArena.from_module(g, dev)
     opt = WD.make_optimizer(g)
-    fs = WD.FusedWideDeepStep(g, opt)
+    fs = FusedWideDeepStep(g, opt)
     assert fs.ok(B)
     xs = (dense.to(dev), cat.to(dev))
     ys = label.to(dev)
@@ -74,7 +75,7 @@ def test_fused_widedeep_step_dp_gradients_match_layerwise():
     dense, cat, label = WD.synth_taxi(B, seed=4)
     m = WD.TaxiWideDeep().to(dev)
     ParamArena.from_module(m, dev)
-    fs = WD.FusedWideDeepStep(m, WD.make_optimizer(m))
+    fs = FusedWideDeepStep(m, WD.make_optimizer(m))
     fs.dp = object()  # any non-None: gradients only (no optimizer in the kernel)
     fs._finish = lambda: None
     fs((dense.to(dev), cat.to(dev)), label.to(dev))
@@ -98,7 +99,7 @@ def test_fused_widedeep_step_declines_batches_beyond_lds():
     the fused step declines and bench_taxi / the trainer run the generic TrainStep path instead."""
     g = WD.TaxiWideDeep().to(dev)
     ParamArena.from_module(g, dev)
-    fs = WD.FusedWideDeepStep(g, WD.make_optimizer(g))
+    fs = FusedWideDeepStep(g, WD.make_optimizer(g))
     assert fs.ok(48) and not fs.ok(64)
 
 
@@ -116,11 +117,11 @@ def test_fused_widedeep_steps_per_execution_matches_single_launches():
         g.load_state_dict(state)
         g = g.to(dev)
         ParamArena.from_module(g, dev)
-        fs = WD.FusedWideDeepStep(g, WD.make_optimizer(g))
+        fs = FusedWideDeepStep(g, WD.make_optimizer(g))
         fs.steps_per_execution = 8
         if multi:
             r = fs.run_resident(xs, ys, n)
-            assert fs._graphU is not None
+            assert fs.steps_per_execution in fs._graphs  # a graph for steps_per_execution steps is in the cache
         else:
             for _ in range(n):
                 r = fs.step_resident(xs, ys)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One rank of a data-parallel v2 taxi run (models/widedeep.py TaxiExchange + FusedWideDeepStep): every
+"""One rank of a data-parallel v2 taxi run (runtime/taxi_step.py TaxiExchange + FusedWideDeepStep): every
 rank trains on its own synthetic examples with the gradients exchanged inside the launch, then writes its
 data, the initial and the final state to <out>/rank<r>.pt for tests/test_taxi_dp_gpu.py (which checks
 the replicas bit-identical and against the fp64 reference of the global batch).  ``--bench K``: also
@@ -39,6 +39,7 @@ def main() -> int:
     from hops_examples_amd.models import widedeep as WD
     from hops_examples_amd.parallel import dist as hdist
     from hops_examples_amd.runtime.arena import ParamArena
+    from hops_examples_amd.runtime.taxi_step import FusedWideDeepStep, TaxiExchange
 
     rank, _, world = hdist.init()
     dev = hdist.device()
@@ -52,8 +53,8 @@ def main() -> int:
     B, nb = a.batch, a.nb
     dense, cat, label = WD.synth_taxi(nb * B, seed=a.seed + 100 + 7 * rank)
     dense, cat, label = dense.view(nb, B, -1), cat.view(nb, B, -1), label.view(nb, B, 1)
-    xdp = WD.TaxiExchange(dev, world)
-    fs = WD.FusedWideDeepStep(m, opt, xdp=xdp)
+    xdp = TaxiExchange(dev, world)
+    fs = FusedWideDeepStep(m, opt, xdp=xdp)
     assert fs.ok(B) and fs.kernel == "v2-dp", fs.kernel
     arena = m.wide.weight._hx_arena
     xdp.sync_replicas(arena)
