@@ -322,6 +322,16 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_maxpool2d_bwd(P<void>(dy), P<unsigned char>(am), P<void>(x), P<void>(dx), B, H, W, C, OH, OW, KH, KW,
                                sh, sw, ph, pw, act, P<float>(colsum), p, P<unsigned long long>(rng), salt, S(st));
   });
+  m.def("maxpool2d_fwd_path", [](u x, u y, u am, int B, int H, int W, int C, int OH, int OW, int KH, int KW, int sh,
+                                 int sw, int ph, int pw) {
+    return hopsx_maxpool2d_fwd_path(P<void>(x), P<void>(y), P<unsigned char>(am), B, H, W, C, OH, OW, KH, KW, sh, sw,
+                                    ph, pw);
+  });
+  m.def("maxpool2d_bwd_path", [](u dy, u am, u x, u dx, int B, int H, int W, int C, int OH, int OW, int KH, int KW,
+                                 int sh, int sw, int ph, int pw, int has_colsum) {
+    return hopsx_maxpool2d_bwd_path(P<void>(dy), P<unsigned char>(am), P<void>(x), P<void>(dx), B, H, W, C, OH, OW, KH,
+                                    KW, sh, sw, ph, pw, has_colsum);
+  });
   m.def("avgpool_global_fwd", [](u x, u y, int B, int HW, int C, u st) {
     return hopsx_avgpool_global_fwd(P<void>(x), P<void>(y), B, HW, C, S(st));
   });

@@ -43,6 +43,16 @@ int hopsx_maxpool2d_fwd(const void* x, void* y, unsigned char* argmax, int B, in
 int hopsx_maxpool2d_bwd(const void* dy, const unsigned char* argmax, const void* x, void* dx, int B, int H, int W,
                         int C, int OH, int OW, int KH, int KW, int sh, int sw, int ph, int pw, int act,
                         float* colsum, float p, const unsigned long long* rng, unsigned salt, hipStream_t st);
+// the kernel the two launchers above choose (their only statement of the choice): 0 scalar (maxpool_fwd_k /
+// maxpool_bwd_k), 1 general vector (maxpool_fwdv_k / maxpool_bwdv_k), 2 non-overlapping fast (maxpool_fwd8_k /
+// maxpool_bwd8_k), -2 refused: an empty window, or more than 256 taps with the 1-byte argmax (the launchers then
+// launch nothing and return -2).  In deterministic mode a backward with a column sum runs the kernel chosen without
+// one (has_colsum counts as 0) and sums the stored dx afterwards.
+int hopsx_maxpool2d_fwd_path(const void* x, const void* y, const unsigned char* argmax, int B, int H, int W, int C,
+                             int OH, int OW, int KH, int KW, int sh, int sw, int ph, int pw);
+int hopsx_maxpool2d_bwd_path(const void* dy, const unsigned char* argmax, const void* x, const void* dx, int B, int H,
+                             int W, int C, int OH, int OW, int KH, int KW, int sh, int sw, int ph, int pw,
+                             int has_colsum);
 int hopsx_avgpool_global_fwd(const void* x, void* y, int B, int HW, int C, hipStream_t st);
 int hopsx_avgpool_global_bwd(const void* dy, void* dx, int B, int HW, int C, hipStream_t st);
 

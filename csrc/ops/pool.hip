@@ -407,16 +407,45 @@ static bool pool_fast(int C, int KH, int KW, int sh, int sw, int ph, int pw, con
          (((uintptr_t)a | (uintptr_t)b | (uintptr_t)d) % 16 == 0) && ((uintptr_t)c % 8 == 0);
 }
 
+// The launchers' choice of kernel, stated once (ops_api.h): 0 scalar, 1 general vector, 2 non-overlapping fast,
+// -2 refused.  The argmax is one byte: tap indices 0 .. 255 fit the scalar kernels (the vector kernels keep 255 for
+// the conv epilogue's dead-ReLU mark and stop at 255 taps); a larger window would store a truncated index and
+// route the gradient to the wrong pixel, so it is refused.
+extern "C" int hopsx_maxpool2d_fwd_path(const void* x, const void* y, const unsigned char* argmax, int B, int H, int W,
+                                        int C, int OH, int OW, int KH, int KW, int sh, int sw, int ph, int pw) {
+  (void)B; (void)H; (void)W; (void)OH; (void)OW;
+  if (KH < 1 || KW < 1 || (argmax && (long)KH * KW > 256)) return -2;
+  if (argmax && pool_fast(C, KH, KW, sh, sw, ph, pw, x, y, argmax, nullptr)) return 2;
+  if ((long)KH * KW <= 255 && pool_vec(C, x, y, argmax, nullptr)) return 1;
+  return 0;
+}
+
+extern "C" int hopsx_maxpool2d_bwd_path(const void* dy, const unsigned char* argmax, const void* x, const void* dx,
+                                        int B, int H, int W, int C, int OH, int OW, int KH, int KW, int sh, int sw,
+                                        int ph, int pw, int has_colsum) {
+  (void)H; (void)W;
+  if (KH < 1 || KW < 1 || (long)KH * KW > 256) return -2;
+  if (has_colsum && hopsx_deterministic()) has_colsum = 0;  // (the detour below: dx first, its column sum after)
+  // (a thread per pooled output walks its whole window: with few outputs and big windows — the E1 model's
+  // 4x4 pool, 6,400 threads in 25 workgroups, 28 us — the per-input-pixel kernel fills the GPU)
+  const bool few_big = (long)B * OH * OW * (C / 8) < 32768 && KH * KW >= 9 && !has_colsum;
+  if (!few_big && pool_fast(C, KH, KW, sh, sw, ph, pw, dy, dx, argmax, x)) return 2;
+  if (!has_colsum && KH * KW <= 255 && pool_vec(C, dy, dx, argmax, x)) return 1;
+  return 0;
+}
+
 extern "C" int hopsx_maxpool2d_fwd(const void* x, void* y, unsigned char* argmax, int B, int H, int W, int C, int OH,
                                    int OW, int KH, int KW, int sh, int sw, int ph, int pw, float p,
                                    const unsigned long long* rng, unsigned salt, hipStream_t st) {
-  if (argmax && pool_fast(C, KH, KW, sh, sw, ph, pw, x, y, argmax, nullptr)) {
+  const int path = hopsx_maxpool2d_fwd_path(x, y, argmax, B, H, W, C, OH, OW, KH, KW, sh, sw, ph, pw);
+  if (path < 0) return path;
+  if (path == 2) {
     const long n8 = (long)B * OH * OW * (C / 8);
     hipLaunchKernelGGL(maxpool_fwd8_k, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, argmax,
                        B, H, W, C, OH, OW, KH, KW, p, rng, salt);
     return (int)hipGetLastError();
   }
-  if (KH * KW <= 255 && pool_vec(C, x, y, argmax, nullptr)) {
+  if (path == 1) {
     const long n8 = (long)B * OH * OW * (C / 8);
     hipLaunchKernelGGL(maxpool_fwdv_k, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, argmax,
                        B, H, W, C, OH, OW, KH, KW, sh, sw, ph, pw, p, rng, salt);
@@ -432,6 +461,9 @@ extern "C" int hopsx_maxpool2d_bwd(const void* dy, const unsigned char* argmax, 
                                    int W, int C, int OH, int OW, int KH, int KW, int sh, int sw, int ph, int pw,
                                    int act, float* colsum, float p, const unsigned long long* rng, unsigned salt,
                                    hipStream_t st) {
+  const int path = hopsx_maxpool2d_bwd_path(dy, argmax, x, dx, B, H, W, C, OH, OW, KH, KW, sh, sw, ph, pw,
+                                            colsum != nullptr);
+  if (path < 0) return path;
   if (colsum && hopsx_deterministic()) {
     // the fused column sum adds through LDS float atomics (unordered even within a workgroup):
     // deterministic mode sums the stored input gradient in a second, turn-ordered pass instead
@@ -440,10 +472,7 @@ extern "C" int hopsx_maxpool2d_bwd(const void* dy, const unsigned char* argmax, 
     return e ? e : hopsx_colsum_bf16(dx, colsum, B * H * W, C, st);
   }
   const size_t shm = colsum ? (size_t)C * sizeof(float) : 0;
-  // (a thread per pooled output walks its whole window: with few outputs and big windows — the E1 model's
-  // 4x4 pool, 6,400 threads in 25 workgroups, 28 us — the per-input-pixel kernel below fills the GPU)
-  const bool few_big = (long)B * OH * OW * (C / 8) < 32768 && KH * KW >= 9 && !colsum;
-  if (!few_big && pool_fast(C, KH, KW, sh, sw, ph, pw, dy, dx, argmax, x)) {
+  if (path == 2) {
     const long n8 = (long)B * OH * OW * (C / 8);
     int g = grid_for(n8);
     if (g > 1024) g = 1024;
@@ -451,7 +480,7 @@ extern "C" int hopsx_maxpool2d_bwd(const void* dy, const unsigned char* argmax, 
                        (bf16_raw*)dx, B, H, W, C, OH, OW, KH, KW, act, colsum, p, rng, salt);
     return (int)hipGetLastError();
   }
-  if (!colsum && KH * KW <= 255 && pool_vec(C, dy, dx, argmax, x)) {
+  if (path == 1) {
     const long n8 = (long)B * H * W * (C / 8);
     hipLaunchKernelGGL(maxpool_bwdv_k, dim3(grid_for(n8)), dim3(256), 0, st, (const bf16_raw*)dy, argmax,
                        (const bf16_raw*)x, (bf16_raw*)dx, B, H, W, C, OH, OW, KH, KW, sh, sw, ph, pw, act, p, rng, salt);

@@ -1325,6 +1325,105 @@ def dropout_reference(h, mask, p: float):
     return (h.float() * torch.where(mask, scale, torch.zeros(()))).to(torch.bfloat16)
 
 
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def _pool_taps(H, W, k, s, p):
+    """For every tap (kh, kw) of the window, in kh-major order: the tap index, the output rows / columns whose tap
+    lies inside the input, and the input rows / columns it reads there (floor-mode output size)."""
+    (KH, KW), (sh, sw), (ph, pw) = _pair(k), _pair(s), _pair(p)
+    OH, OW = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+    for kh in range(KH):
+        ih = torch.arange(OH) * sh - ph + kh
+        oh = torch.nonzero((ih >= 0) & (ih < H)).flatten()
+        for kw in range(KW):
+            iw = torch.arange(OW) * sw - pw + kw
+            ow = torch.nonzero((iw >= 0) & (iw < W)).flatten()
+            yield kh * KW + kw, oh, ow, ih[oh], iw[ow]
+
+
+def pool_reference(x, k, s, p, dtype=torch.float64):
+    """Plain-tensor statement of pool.hip's max-pool forward for NHWC ``x`` [B, H, W, C] on the host: returns
+    ``(y, argmax)`` with ``y`` the maximum over the window's in-bounds taps (in ``dtype``) and ``argmax`` (uint8)
+    the tap index ``kh * KW + kw`` of the FIRST maximum in kh-major order; the index runs over the full window,
+    padded taps are skipped.  Output size is floor-mode (kernels.pool_out)."""
+    (KH, KW), (sh, sw), (ph, pw) = _pair(k), _pair(s), _pair(p)
+    B, H, W, C = x.shape
+    OH, OW = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+    xd = x.to(dtype)
+    y = torch.full((B, OH, OW, C), float("-inf"), dtype=dtype)
+    am = torch.zeros((B, OH, OW, C), dtype=torch.int64)
+    seen = torch.zeros((B, OH, OW, C), dtype=torch.bool)
+    for tap, oh, ow, ih, iw in _pool_taps(H, W, k, s, p):
+        if oh.numel() == 0 or ow.numel() == 0:
+            continue
+        o = (slice(None), oh[:, None], ow[None, :])
+        v = xd[:, ih[:, None], iw[None, :]]
+        take = ~seen[o] | (v > y[o])  # the first in-bounds tap, then only a strictly larger one
+        y[o] = torch.where(take, v, y[o])
+        am[o] = torch.where(take, torch.full_like(am[o], tap), am[o])
+        seen[o] = True
+    return y, am.to(torch.uint8)
+
+
+def pool_bwd_reference(dy, argmax, x_shape, k, s, p, x=None, act=None, mask=None, drop_p: float = 0.0,
+                       dtype=torch.float64):
+    """Plain-tensor statement of pool.hip's max-pool backward: returns ``(dx, colsum_increment)``, both unrounded.
+    The gradient of every pooled output, first multiplied by ``mask / (1 - float32(drop_p))`` when ``mask`` (the
+    fused Dropout's keep mask, on the pooled output) is given, goes to the input pixel of its ``argmax`` tap (an
+    argmax byte that names no tap of the window, the conv epilogue's 0xFF, gives nothing).  The total at every
+    input pixel is multiplied by ``act'`` expressed through the pool input ``x`` (the relu / sigmoid / tanh forms
+    of common.h act_grad_from_out; without ``x`` no ``act'`` is applied, as in the kernels).  Pixels no window
+    covers, the floor-mode remainder rows and columns among them, are zero.  ``colsum_increment`` [C] is the
+    per-channel sum of that ``dx``."""
+    B, H, W, C = x_shape
+    g = dy.to(dtype)
+    if mask is not None:
+        scale = (1.0 / (1.0 - torch.tensor(drop_p, dtype=torch.float32))).to(dtype)
+        g = g * mask.to(dtype) * scale
+    am = argmax.to(torch.int64)
+    dx = torch.zeros(B, H, W, C, dtype=dtype)
+    for tap, oh, ow, ih, iw in _pool_taps(H, W, k, s, p):
+        if oh.numel() == 0 or ow.numel() == 0:
+            continue
+        o = (slice(None), oh[:, None], ow[None, :])
+        # (one tap: distinct outputs read distinct input pixels, so the indexed add has no duplicates)
+        dx[:, ih[:, None], iw[None, :]] += torch.where(am[o] == tap, g[o], torch.zeros((), dtype=dtype))
+    name = {0: None, "none": None, 1: "relu", 2: "sigmoid", 3: "tanh"}.get(act, act)
+    if x is not None and name is not None:
+        xd = x.to(dtype)
+        dx = dx * {"relu": lambda v: (v > 0).to(dtype), "sigmoid": lambda v: v * (1 - v),
+                   "tanh": lambda v: 1 - v * v}[name](xd)
+    return dx, dx.sum((0, 1, 2))
+
+
+def gap_reference(x, dtype=torch.float64):
+    """Global average pool of NHWC ``x``: the mean over H x W, [B, C], unrounded."""
+    return x.to(dtype).mean((1, 2))
+
+
+def gap_bwd_reference(dy, x_shape, dtype=torch.float64):
+    """Its backward: ``dy / (H W)`` at every pixel, [B, H, W, C], unrounded."""
+    B, H, W, C = x_shape
+    return (dy.to(dtype) / (H * W)).view(B, 1, 1, C).expand(B, H, W, C).contiguous()
+
+
+def dropout_keep_reference(rng, salt: int, shape, p: float):
+    """The keep mask of a Dropout over a tensor of ``shape``, stated on the host: runtime.persist.dropout_keep at
+    the LINEAR index of every element (for the Dropout fused into the max-pool: the NHWC index of the pooled
+    output, which forward and backward both hash), thresholded with ``float32(p)``.  ``rng``: the two words
+    (seed, step counter) of the device RNG state."""
+    from ..runtime.persist import dropout_keep
+
+    n = 1
+    for d in shape:
+        n *= int(d)
+    seed, ctr = (int(v) & ((1 << 64) - 1) for v in (rng.tolist() if torch.is_tensor(rng) else rng))
+    p32 = float(torch.tensor(p, dtype=torch.float32))
+    return dropout_keep(seed, ctr, int(salt) & 0xFFFFFFFF, torch.arange(n, dtype=torch.int64), p32).view(*shape)
+
+
 def loss_and_grad(logits, target, kind: str = "sparse_ce"):
     """Non-autograd fused loss for training loops that seed backward themselves:
     returns (mean loss [1], correct [1] int32, count, dlogits in the logits' dtype).

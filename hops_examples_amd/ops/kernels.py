@@ -446,6 +446,29 @@ def maxpool2d_bwd(dy, argmax, x_shape, k, s, p, x=None, act=0, out=None, colsum=
     return out
 
 
+def maxpool_fwd_path(x, k, s, p, out=None, argmax=None, drop_p=0.0, rng=None, salt=0):
+    """The kernel maxpool2d_fwd runs for these arguments: 0 scalar, 1 general vector, 2 non-overlapping fast,
+    -2 refused (the launcher's own decision, csrc/ops/pool.hip hopsx_maxpool2d_fwd_path)."""
+    B, H, W, C = x.shape
+    OH, OW = pool_out(H, W, k, s, p)
+    if out is None:
+        out = torch.empty(B, OH, OW, C, device=x.device, dtype=BF16)
+    if argmax is None:
+        argmax = torch.empty(B, OH, OW, C, device=x.device, dtype=torch.uint8)
+    return _C.ext().maxpool2d_fwd_path(ptr(x), ptr(out), ptr(argmax), B, H, W, C, OH, OW, k[0], k[1], s[0], s[1],
+                                       p[0], p[1])
+
+
+def maxpool_bwd_path(dy, argmax, x_shape, k, s, p, x=None, act=0, out=None, colsum=None, drop_p=0.0, rng=None, salt=0):
+    """The kernel maxpool2d_bwd runs for these arguments (as maxpool_fwd_path)."""
+    B, H, W, C = x_shape
+    OH, OW = dy.shape[1], dy.shape[2]
+    if out is None:
+        out = torch.empty(B, H, W, C, device=dy.device, dtype=BF16)
+    return _C.ext().maxpool2d_bwd_path(ptr(dy), ptr(argmax), ptr(x), ptr(out), B, H, W, C, OH, OW, k[0], k[1], s[0],
+                                       s[1], p[0], p[1], int(colsum is not None))
+
+
 def gap_fwd(x, out=None):
     B, H, W, C = x.shape
     if out is None:
