@@ -26,8 +26,8 @@
 //   B  dh (+ h, dlogits, loss) of each image -> every position workgroup (and every head: each head
 //      recomputes the fc2 / fc1-bias gradient from all 32 payloads and applies the SAME Adadelta
 //      update to its replicated copy of those 1,418 params — bit-identical, no reduction hop);
-//   C  conv-parameter gradient partials (8,416 fp32) per position -> 162 slice owners (52 params
-//      each) reduce over the 169 partials in a fixed order and run Adadelta on their slice;
+//   C  conv-parameter gradient partials (8,416 fp32) per position -> 132 slice owners (64 params = two
+//      128-byte lines each) reduce over the 169 partials in a fixed order and run Adadelta on their slice;
 //   D  the updated conv parameters -> every position workgroup (next step's forward).
 // Hand-off form: MI355X_MICROARCH.md "Valid forms" table, row 1 (cdna_hip_programming §6 G16 R1):
 // payload stored write-through (16-B `sc1` buffer stores), every storing wave drains vmcnt, a
@@ -65,8 +65,15 @@ constexpr int B = 32;  // images per step
 // (one position workgroup per pooled position: NPOS of them)
 constexpr int NCONV = C2 * 128 + C2 + C1 * 4 + C1;  // 8416 conv params: [w2 | b2 | w1 | b1]
 constexpr int OFF_B2 = C2 * 128, OFF_W1 = OFF_B2 + C2, OFF_B1 = OFF_W1 + C1 * 4;
-constexpr int SLICE = 52, NSLICE = (NCONV + SLICE - 1) / SLICE;  // 162 slice owners
+// A slice is two whole 128-byte lines of a slabC row (the rows are 128-byte aligned: NCONV * 4 = 263 * 128), so
+// an owner fetches exactly the lines it uses and no line is fetched by two owners; the conv2 weights end on a
+// slice boundary (OFF_B2 = 128 slices), so an owner publishes either one whole bf16 line of D or two whole fp32
+// lines.  Which workgroup owns an element changes no bit: its sum over the positions and its Adadelta are
+// element-wise
+constexpr int SLICE = 64, NSLICE = (NCONV + SLICE - 1) / SLICE;  // 132 slice owners (131 is half filled)
 constexpr int NRED = 19;                                           // partial groups in the slice reduce
+constexpr int NKC = (NPOS + NRED - 1) / NRED;                      // 9 partials per group: pp = g + NRED k
+constexpr int NQ = SLICE / 4;                                      // 16-byte quads per slice row
 constexpr int NHEAD = B;
 constexpr int GRID = NPOS + NHEAD;  // 201 workgroups, one per CU
 constexpr int PAY = 272;            // head payload floats
@@ -106,7 +113,7 @@ constexpr int L_DH = L_AM + B * C2;               // bf16 [32 b][DHS]
 constexpr int L_DC2 = L_DH + B * DHS * 2;         // bf16 [64 co][DCS] conv2 output grad, (b,q) cols
 constexpr int L_STG = L_DC2 + C2 * DCS * 2;       // f32  staging: A partial [32][128] / C grads [8416]
 constexpr int L_RED = L_STG + NCONV * 4;          // f32  [NRED][SLICE] slice reduce / conv1 grad halves
-constexpr int L_SL = L_RED + 1024 * 4;            // f32  [3][SLICE] owned conv slice: master, s1, s2
+constexpr int L_SL = L_RED + NRED * SLICE * 4;    // f32  [3][SLICE] owned conv slice: master, s1, s2
 constexpr int L_KEEP = L_SL + 3 * 64 * 4;         // u8   [32 b][64] next step's dropout keep mask
 constexpr int LDS_BYTES = L_KEEP + B * C2;
 
@@ -140,8 +147,15 @@ constexpr long XO_POOL = 0, XO_DHT = XO_POOL + 2L * XMAX * XS_POOL, XO_FC2 = XO_
 constexpr int XF_POOL = 0, XF_H = XMAX * NPOS, XF_CONV = XF_H + XMAX, XF_WORDS = XF_CONV + XMAX * NSLICE;
 static_assert(NFC2 <= NFC2P && NFC2P % 4 == 0 && X_BYTES < 0x7fffffffL, "exchange geometry");
 static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU: 160 KiB LDS");
-static_assert(L_RED + NRED * SLICE * 4 <= L_SL && 2 * 32 * 5 * 4 <= 1024 * 4, "reduce scratch");
-static_assert(NRED * 13 <= 256 && NSLICE * SLICE >= NCONV && NSLICE <= NPOS, "slice geometry");
+static_assert(L_RED + NRED * SLICE * 4 <= L_SL && 2 * 32 * 5 * 4 <= NRED * SLICE * 4, "reduce scratch");
+static_assert(SLICE * 4 % 128 == 0 && NCONV * 4 % 128 == 0, "a slice row is whole 128-byte lines of an aligned slabC row");
+static_assert(OFF_B2 % SLICE == 0 && D_F32 % 128 == 0 && D_BYTES % 128 == 0, "no slice straddles the bf16 / fp32 parts of D");
+static_assert(NSLICE * SLICE >= NCONV && NSLICE <= NPOS && SLICE == 64, "slice geometry: one wave updates a slice");
+// the owners' gather: wave w (of 4) loads groups 4w .. 4w + 3, 16 lanes (one quad each) per group, so one wave
+// instruction reads 4 whole rows; groups 16 .. NRED - 1 are a second item on the last 16 lanes of waves
+// 0 .. NRED - 17
+static_assert(NQ == 16 && NRED > 16 && NRED - 16 <= 3 && 5 * NKC <= 64 && 2 * NKC <= 32 && NRED * (NKC - 1) < NPOS,
+              "gather geometry: at most 5 groups' flags per wave, one per lane; both items' rows in one pend mask");
 
 struct Args {
   float* master;      // arena fp32 parameters
@@ -1014,66 +1028,68 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       if (tid == 0) flag_store(a.flags + FL_C + p, ep);
     }
     stamp(a, s, 6);
-    // ---- slice owners: fixed-order reduce of 52 params over the 169 partials, Adadelta, publish D ----
+    // ---- slice owners: fixed-order reduce of 64 params over the 169 partials, Adadelta, publish D ----
     if (owner) {
       const int e0 = p * SLICE;
-      constexpr int NKC = (NPOS + NRED - 1) / NRED;  // 9 partials per thread
-      static_assert(6 * NKC <= 64, "the flags of a wave's groups (64 threads span at most 6 groups of 13): one per lane");
+      // Item (g, j): quad j (16 bytes) of the slice's row in the partials pp = g + 19 k of group g, k < 9, summed in
+      // that order into RED[g].  Wave w holds groups 4w .. 4w + 3, 16 lanes each (thread = 16 g + j), so one wave
+      // instruction reads 4 whole rows of the slice (2 whole 128-byte lines each) and nothing else; groups 16 .. 18
+      // are a second item (rows 9 .. 17 of the thread) on the last 16 lanes of waves 0 .. 2, in flight with the
+      // first.  A row past the end of the slice (slice 131 is half filled) is not loaded: RED gets its zeros
+      const int j = lane & (NQ - 1), lq = lane >> 4, g = 4 * w + lq, gx = 16 + w;
+      const bool act = e0 + 4 * j < NCONV, two = lq == 3 && gx < NRED;
+      const auto R = rsrc(a.slabC + (long)par * NPOS * NCONV);
+      f32x4 v[2 * NKC];
+#pragma unroll
+      for (int k = 0; k < 2 * NKC; ++k) v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      auto load = [&](int k) {
+        const int pp = k < NKC ? g + NRED * k : gx + NRED * (k - NKC);
+        v[k] = bld16<SC1>(R, (pp * NCONV + e0 + 4 * j) * 4);
+      };
+      // the rows this thread loads: all 9 of its first group (g < 16), and of the second the 9 or 8 that exist
+      const unsigned rows2 = gx + NRED * (NKC - 1) < NPOS ? (1u << NKC) - 1u : (1u << (NKC - 1)) - 1u;
+      const unsigned pend = !act ? 0u : ((1u << NKC) - 1u) | (two ? rows2 << NKC : 0u);
+      bool lost = false;  // the flag form's wait gave up (uniform)
       if ((a.hand & 8) && !a.acquire) {
-        // progressive form (HOPSX_PERSIST_PROG bit 1): thread (g, j) loads its partials pp = g + 19 k as their
-        // flags arrive.  Wave w holds groups g0 .. g1 (at most 6, a group split over two waves is polled by
-        // both); its lane l polls the flag of group g0 + l / 9, partial k = l % 9: bit (g - g0) * 9 + k of the
-        // ballot is this thread's row k
-        const int j = tid % 13, g = tid / 13;
-        const bool act = g < NRED && e0 + 4 * j < NCONV;
-        const int g0 = (w * 64) / 13, g1 = (w * 64 + 63) / 13;
-        const int lg = g0 + lane / NKC, lp = lg + NRED * (lane % NKC);
-        const bool mine = lane < 6 * NKC && lg <= g1 && lg < NRED && lp < NPOS;
-        const auto R = rsrc(a.slabC + (long)par * NPOS * NCONV);
-        f32x4 v[NKC];
-#pragma unroll
-        for (int k = 0; k < NKC; ++k) v[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const unsigned pend = !act ? 0u : (g + NRED * (NKC - 1) < NPOS ? (1u << NKC) - 1u : (1u << (NKC - 1)) - 1u);
-        gather_rows<NKC>(a.flags + FL_C + lp, mine, act ? (g - g0) * NKC : 0, pend, ep, a.err, ecode(3, s), s_ok + 2,
-                         a.tmo, [&](int k) { v[k] = bld16<SC1>(R, ((g + NRED * k) * NCONV + e0 + 4 * j) * 4); });
+        // progressive form (HOPSX_PERSIST_PROG bit 1): the rows are loaded as their flags arrive.  Lane l < 36 of
+        // wave w polls the flag of group 4w + l / 9, partial k = l % 9, lanes 36 .. 44 of waves 0 .. 2 those of
+        // group 16 + w: bit 9 lq + k of the ballot is this thread's row k, and for the threads with a second item
+        // (lq = 3) bits 36 .. 44 follow as its rows 9 .. 17
+        const int lp = lane < 4 * NKC ? 4 * w + lane / NKC + NRED * (lane % NKC) : gx + NRED * (lane - 4 * NKC);
+        const bool mine = lane < 4 * NKC || (gx < NRED && lane < 5 * NKC && lp < NPOS);
+        gather_rows<2 * NKC>(a.flags + FL_C + lp, mine, lq * NKC, pend, ep, a.err, ecode(3, s), s_ok + 2, a.tmo, load);
         stamp(a, s, 7);  // (the partials' load is inside the wait in this form)
-        // every lane names its partial registers here, so the compiler waits for the loads on every path into the
-        // sum (the sum's lanes wait here anyway).  Left to the conditional sum, its bookkeeping keeps them pending
-        // along the path around it and waits vmcnt(0) where those registers are next written: that landed behind
-        // the D flag store, and wave 0 waited out the store's round trip (0.5 us) before its fc1 Adadelta
-#pragma unroll
-        for (int k = 0; k < NKC; ++k) asm volatile("" ::"v"(v[k]));
-        if (g < NRED) {
-          f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int k = 0; k < NKC; ++k) acc += v[k];
-          *(f32x4*)(RED + g * SLICE + 4 * j) = acc;
-        }
-        __syncthreads();
-        const int f = s_ok[2];
-        if (f) return;
       } else {
-      if (!wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger, (a.hand & 2)))
-        return;
-      stamp(a, s, 7);
-      if (tid < 13 * NRED) {
-        const int j = tid % 13, g = tid / 13;
+        lost = !wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger,
+                         (a.hand & 2));
+        stamp(a, s, 7);
+#pragma unroll
+        for (int k = 0; k < 2 * NKC; ++k)  // every row in flight before the sum
+          if (!lost && ((pend >> k) & 1u)) load(k);
+      }
+      // every lane names its partial registers here, on EVERY path out of the two forms (a lost wait leaves below,
+      // behind the sum), so the compiler waits for the loads here, where the sum's lanes wait anyway.  On a path
+      // around this use its bookkeeping keeps them pending and waits vmcnt(0) where those registers are next
+      // written: that landed behind the D flag store, and wave 0 waited out the store's round trip (0.5 - 0.7 us)
+      // before its fc1 Adadelta (seen twice: a conditional sum, and an early return of the flag form)
+#pragma unroll
+      for (int k = 0; k < 2 * NKC; ++k) asm volatile("" ::"v"(v[k]));
+      {
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (e0 + 4 * j < NCONV) {
-          const auto R = rsrc(a.slabC + (long)par * NPOS * NCONV);
-          constexpr int NK = (NPOS + NRED - 1) / NRED;  // 9 partials per thread, all in flight
-          f32x4 v[NK];
 #pragma unroll
-          for (int k = 0; k < NK; ++k) {
-            const int pp = g + NRED * k;
-            v[k] = pp < NPOS ? bld16<SC1>(R, (pp * NCONV + e0 + 4 * j) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-          }
-#pragma unroll
-          for (int k = 0; k < NK; ++k) acc += v[k];
-        }
+        for (int k = 0; k < NKC; ++k) acc += v[k];
         *(f32x4*)(RED + g * SLICE + 4 * j) = acc;
       }
+      if (two) {
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < NKC; ++k) acc += v[NKC + k];
+        *(f32x4*)(RED + gx * SLICE + 4 * j) = acc;
+      }
       __syncthreads();
+      {
+        const int f = s_ok[2];  // (a wave of the progressive gather gave up)
+        if (lost || f) return;
       }
       const int e = e0 + tid;
       float gs = 0.f;
@@ -1106,26 +1122,25 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           gs = t;
         }
       }
-      if (tid < SLICE) {  // wave 0
+      if (w == 0) {  // one full wave: lane = element of the slice (SLICE == 64)
         float wn = 0.f;
         if (e < NCONV) {
           SLm[tid] = adadelta(SLm[tid], gs * hp.gscale, SL1[tid], SL2[tid], hp);
           wn = SLm[tid];
         }
-        // the D payload: conv2 weights as bf16 pairs (slices start at even indices), the rest fp32; every
-        // store a 4-byte write-through (sc1) store
+        // the D payload, whole 128-byte lines written by ONE store instruction of this wave (4-byte write-through
+        // sc1 stores): an owner of conv2 weights its line of 64 bf16 (pairs, the even lanes), the four owners of
+        // the small parameters their two lines of fp32 (slice 131: one, it is half filled)
         const float wnext = __shfl_down(wn, 1, 64);
         unsigned char* D = (unsigned char*)a.slabD + (long)par * D_BYTES;
-        if (e < OFF_B2) {
-          if (!(tid & 1))
+        if (p < OFF_B2 / SLICE) {
+          if (!(lane & 1))
             __hip_atomic_store((gu32*)(D + e * 2), (unsigned)f2bf_hw(wn) | ((unsigned)f2bf_hw(wnext) << 16),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (e < NCONV) {
           __hip_atomic_store((gu32*)(D + D_F32 + (e - OFF_B2) * 4), __float_as_uint(wn), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
         }
-      }
-      if (w == 0) {
         drain();
         if (lane == 0) flag_store(a.flags + FL_D + p, ep);
       }
@@ -1200,6 +1215,21 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     if (s + 1 < a.nsteps) draw_keep(s + 1);  // KEEP is next read after the D wait's barrier
     stamp(a, s, 9);
     // ---- D: the updated conv parameters for the next step ----
+    if (!owner && tid < 64) {
+      // The NPOS - NSLICE positions that own no slice get here ~5 us before the owners publish.  Polling every flag
+      // line all that time delays the owners' flag stores to those lines (last D publish -> D ready 1.1 -> 1.8 us
+      // for the earliest position with 37 such pollers instead of 7, profiles/r15_persist_aligned_slices.txt).  So
+      // they first watch ONE line, the flags of the four owners of the small parameters, from four lanes; the gate
+      // only delays the wait below, which checks every flag and the error word: it is bounded by time alone
+      constexpr int G0 = OFF_B2 / SLICE;
+      const bool mine = lane < NSLICE - G0;
+      const long long t0 = wall_clock64();
+      for (;;) {
+        const unsigned f = mine ? flag_load(a.flags + FL_D + G0 + lane) : ep;
+        if (__all(f == ep) || wall_clock64() - t0 > 2000) break;  // (20 us: far longer than the owners' phase)
+        __builtin_amdgcn_s_sleep(4);
+      }
+    }
     if (!wait_all(a.flags + FL_D, NSLICE, ep, a.err, ecode(4, s), a.acquire, s_ok, a.tmo, a.pollw_d, a.stagger,
                   (a.hand & 2)))
       return;
@@ -1657,6 +1687,8 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.err = (unsigned*)p[15];
   a.out = (float*)p[16];
   a.dbg = (unsigned long long*)p[17];
+  // the slice owners read whole 128-byte lines of slabC and write whole lines of slabD: both line-aligned
+  if (((uint64_t)a.slabC & 127) || ((uint64_t)a.slabD & 127)) return (int)hipErrorInvalidValue;
   for (int k = 0; k < 8; ++k) a.off[k] = iv[k];
   a.nbatch = iv[8];
   a.salt = (unsigned)iv[9];

@@ -76,8 +76,9 @@ def timing(n, reps=5, loopback=0):
         ts.append((time.perf_counter() - t0) / n * 1e6)
     eng.check()
     st = eng.phase_stamps(n).cpu().double() * 0.01  # us
-    pos, head = st[:169], st[169:]
-    own = pos[:162]
+    geom = persist.geometry()
+    pos, head = st[:geom["npos"]], st[geom["npos"]:]
+    own = pos[:geom["nslice"]]  # the slice owners are the first positions
     step_us = (pos[:, 2:, 0] - pos[:, 1:-1, 0]).median().item()
     print(f"[loopback {loopback}] host wall {min(ts):.2f} us/step (best of {reps}), in-kernel step {step_us:.2f} us")
     # launch boundaries (stamps 13: workgroup entry in step 0, 14: write-back issued in the last step)
