@@ -113,6 +113,11 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_conv2d_fwd(P<void>(x), P<void>(w), g.data(), epi, P<void>(out), P<float>(bias), act,
                             P<float>(colsum), xscale, xshift, S(st));
   });
+  m.def("conv2d_fwd_res", [](u x, u w, std::vector<int> g, u out, u bias, int act, u residual, u st) {
+    return hopsx_conv2d_fwd_res(P<void>(x), P<void>(w), g.data(), P<void>(out), P<float>(bias), act,
+                                P<void>(residual), S(st));
+  });
+  m.def("conv2d_fwd_res_path", [](std::vector<int> g) { return hopsx_conv2d_fwd_res_path(g.data()); });
   m.def("conv2d_dgrad", [](u dy, u w, std::vector<int> g, u dx, u yprev, int act, u colsum, u y, int yact, u addend,
                            u st) {
     return hopsx_conv2d_dgrad(P<void>(dy), P<void>(w), g.data(), P<void>(dx), P<void>(yprev), act, P<float>(colsum),

@@ -526,11 +526,15 @@ static bool gg_big_spatial(const int* geom) {
          !hopsx_disabled("gg_stem") && !hopsx_disabled("gg_n64") && !hopsx_deterministic();
 }
 
+// the forward conv shapes the gg engine is asked for at all (launch_gg / gg_takes then decide on the plan)
+static bool gg_conv_fwd_ok(const void* x, const void* w, const ConvGeom& g) {
+  return !(g.C % 8 || g.CO % 8 || ((uintptr_t)x | (uintptr_t)w) % 16 || hopsx_disabled("gg_fwd") || gg_narrow(g, g.CO));
+}
+
 template <class EP>
 static bool gg_conv_fwd(const void* x, const void* w, const ConvGeom& g, const EP& e, hipStream_t st) {
   const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
-  if (g.C % 8 || g.CO % 8 || ((uintptr_t)x | (uintptr_t)w) % 16 || hopsx_disabled("gg_fwd") || gg_narrow(g, N))
-    return false;
+  if (!gg_conv_fwd_ok(x, w, g)) return false;
   const GgDense ws{(const bf16_raw*)w, (long)K, N, K};
   if (gg_1x1(g)) return launch_gg<true, true>(GgDense{(const bf16_raw*)x, (long)g.C, M, K}, ws, e, M, N, K, false, st);
   return launch_gg<true, true>(GgIm2col{(const bf16_raw*)x, g, M, K}, ws, e, M, N, K, false, st);
@@ -660,6 +664,58 @@ extern "C" int hopsx_conv2d_fwd(const void* x, const void* w, const int* geom, i
   } else {
     return -2;
   }
+  return (int)hipGetLastError();
+}
+
+// ---- forward with a residual (frozen inference: BatchNorm folded into w / bias, the block's shortcut added
+// before the activation).  The route is hopsx_conv2d_fwd's for a bf16 store without column sums, decided here
+// once for the launcher and for the query; the direct input-layer kernel is not among them.
+enum ConvResRoute : int { RES_MFMA = 0, RES_GG = 1, RES_GEMM = 2, RES_SPLITK = 3 };
+
+// x / w / out: the operands (the query passes aligned dummies); the same tests, in the same order, as
+// hopsx_conv2d_fwd's bf16-store branch
+static int conv_res_route(const int* geom, const ConvGeom& g, const void* x, const void* w, const void* out,
+                          float** ws, unsigned** tk) {
+  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
+  if (hopsx_conv_fwd_mfma_ok(geom) && !gg_big_spatial(geom) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) &&
+      ((uintptr_t)out % 16 == 0))
+    return RES_MFMA;
+  GgPlan p;
+  if (gg_conv_fwd_ok(x, w, g) && gg_takes(M, N, K, false, p)) return RES_GG;
+  return conv_split(0, M, N, K, ws, tk) ? RES_SPLITK : RES_GEMM;
+}
+
+extern "C" int hopsx_conv2d_fwd_res_path(const int* geom) {
+  const ConvGeom g = make_geom(geom);
+  float* ws;
+  unsigned* tk;
+  return conv_res_route(geom, g, nullptr, nullptr, nullptr, &ws, &tk);
+}
+
+extern "C" int hopsx_conv2d_fwd_res(const void* x, const void* w, const int* geom, void* out, const float* bias,
+                                    int act, const void* residual, hipStream_t st) {
+  if (!residual) return hopsx_conv2d_fwd(x, w, geom, EPI_STORE_BF16, out, bias, act, nullptr, 0.f, 0.f, st);
+  if (act != ACT_NONE && act != ACT_RELU) return -2;
+  const ConvGeom g = make_geom(geom);
+  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
+  if ((uintptr_t)residual % 16) return -4;
+  const uintptr_t ro = (uintptr_t)residual, oo = (uintptr_t)out, nb = (uintptr_t)M * N * sizeof(bf16_raw);
+  if (ro < oo + nb && oo < ro + nb) return -5;
+  float* ws = nullptr;
+  unsigned* tk = nullptr;
+  const int route = conv_res_route(geom, g, x, w, out, &ws, &tk);
+  if (route == RES_MFMA) return hopsx_conv2d_fwd_mfma_res(x, w, geom, out, bias, act, residual, st);
+  const EpiStoreResBF16 e{(bf16_raw*)out, N, bias, 1.f, act, nullptr, (const bf16_raw*)residual};
+  if (route == RES_GG) return gg_conv_fwd(x, w, g, e, st) ? (int)hipGetLastError() : -6;  // (the plan said yes)
+  Im2colLoader al{(const bf16_raw*)x, g, (g.C % 8 == 0) && ((uintptr_t)x % 16 == 0)};
+  DenseLoader bl{(const bf16_raw*)w, K, is_vec_ok(w, K)};
+  if (route == RES_SPLITK) {
+    const SplitFinish f{tk, kEpiStoreResBF16, out, N, bias, 1.f, 0.f, act, nullptr, 0, nullptr,
+                        (const bf16_raw*)residual};
+    launch_gemm<true, true>(al, bl, EpiAtomicTicketRes{{ws, N, 1.f, nullptr, f}}, M, N, K, true, st);
+    return (int)hipGetLastError();
+  }
+  launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
   return (int)hipGetLastError();
 }
 

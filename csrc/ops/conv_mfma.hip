@@ -112,13 +112,20 @@ struct InBn {
   int act;
 };
 
+//
+// RES: out = act(acc + bias + res) — the last conv of a residual block at frozen inference (BatchNorm folded
+// into w / bias): the shortcut `res` (bf16, y's layout, never aliasing y) is added before the activation.
+// Its 16 rows per pixel group are loaded as 16-B vectors in the store loop's (row, chunk) map before the
+// MFMAs, pass through the wave's LDS scratch and are read back in the C-fragment map, where the dgrad
+// kernel's epilogue reads its act' operand.
 template <int NF, int KS, bool POOL = false, int UN = CM_UN, bool BNS = false, int T0 = 0, int PK = 2,
-          bool IBN = false>
+          bool IBN = false, bool RES = false>
 __global__ __launch_bounds__(256) void conv_fwd_mfma_k(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w,
                                                       const float* __restrict__ bias, bf16_raw* __restrict__ y,
                                                       ConvGeom g, int act, int K, PoolEpi pe = PoolEpi{},
                                                       float* __restrict__ bnacc = nullptr, In0 i0 = In0{},
-                                                      InBn ib = InBn{}) {
+                                                      InBn ib = InBn{}, const bf16_raw* __restrict__ res = nullptr) {
+  static_assert(!RES || (!POOL && !BNS && T0 == 0 && !IBN), "the residual epilogue is the plain forward's");
   constexpr int CO = NF * 16;
   extern __shared__ __attribute__((aligned(16))) bf16_raw cm_smem[];
   constexpr int cpr = KS * 4;  // 16-B chunks per weight row (K padded to 32*KS)
@@ -335,6 +342,18 @@ __global__ __launch_bounds__(256) void conv_fwd_mfma_k(const bf16_raw* __restric
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       if (g0 + u >= ngroups) break;
+      // RES: this group's shortcut rows, in flight under the MFMAs (rows past M read row 0 and are never stored)
+      constexpr int NRC = RES ? (16 * CO / 8 + 63) / 64 : 1;
+      bf16x8 rres[NRC];
+      if constexpr (RES) {
+#pragma unroll
+        for (int q = 0; q < NRC; ++q) {
+          const int c = lane + 64 * q;
+          const int row = c / (CO / 8), col = (c - row * (CO / 8)) * 8;
+          const bool ok = c < 16 * CO / 8 && (g0 + u) * 16 + row < M;
+          rres[q] = *(const bf16x8*)(res + (ok ? (long)((g0 + u) * 16 + row) * CO + col : 0));
+        }
+      }
       f32x4 acc[NF];
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) acc[nf] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -417,11 +436,24 @@ __global__ __launch_bounds__(256) void conv_fwd_mfma_k(const bf16_raw* __restric
       }
       // epilogue through the wave's LDS scratch: C map col = lane&15 (co), row = (lane>>4)*4 + r (pixel)
       const int base = (g0 + u) * 16;
+      if constexpr (RES) {
+        // shortcut rows -> scratch [16][CO]; each lane then reads and overwrites only its own C-map slots
+#pragma unroll
+        for (int q = 0; q < NRC; ++q) {
+          const int c = lane + 64 * q;
+          const int row = c / (CO / 8), col = (c - row * (CO / 8)) * 8;
+          if (c < 16 * CO / 8) *(bf16x8*)(sc + row * CO + col) = rres[q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+      }
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const bf16_raw o = f2bf(apply_act(acc[nf][r] + bv[nf], act));
+          float pre = acc[nf][r] + bv[nf];
+          if constexpr (RES) pre += bf2f(sc[(fq * 4 + r) * CO + nf * 16 + fr]);
+          const bf16_raw o = f2bf(apply_act(pre, act));
           sc[(fq * 4 + r) * CO + nf * 16 + fr] = o;
           if constexpr (BNS) {
             const float v = base + fq * 4 + r < M ? bf2f(o) : 0.f;
@@ -1167,9 +1199,10 @@ extern "C" int hopsx_conv2d_fwd_mfma(const void* x, const void* w, const int* ge
   return hopsx_conv2d_fwd_mfma_ex(x, w, geom, out, bias, act, nullptr, st);
 }
 
-// bnacc != null: also accumulate the BatchNorm statistics of the output (conv_fwd_mfma_k BNS)
-extern "C" int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int* geom, void* out, const float* bias,
-                                        int act, float* bnacc, hipStream_t st) {
+// bnacc != null: also accumulate the BatchNorm statistics of the output (conv_fwd_mfma_k BNS); res != null (never
+// with bnacc): out = act(conv + bias + res) (conv_fwd_mfma_k RES)
+static int fwd_mfma_impl(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
+                         float* bnacc, const void* res, hipStream_t st) {
   ConvGeom g;
   g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
   g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
@@ -1181,7 +1214,11 @@ extern "C" int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int*
   const int grid = cm_grid((M + 15) / 16);
   const size_t shm = (size_t)(g.CO * cm_rs(KS * 4) * 8 + CM_WAVES * 16 * g.CO) * sizeof(bf16_raw);
 #define HOPSX_CMF(NF, KSV)                                                                                     \
-  if (bnacc)                                                                                                   \
+  if (res)                                                                                                     \
+    hipLaunchKernelGGL((conv_fwd_mfma_k<NF, KSV, false, CM_UN, false, 0, 2, false, true>), dim3(grid), dim3(256), \
+                       shm, st, (const bf16_raw*)x, (const bf16_raw*)w, bias, (bf16_raw*)out, g, act, K, PoolEpi{}, \
+                       nullptr, In0{}, InBn{}, (const bf16_raw*)res);                                            \
+  else if (bnacc)                                                                                              \
     hipLaunchKernelGGL((conv_fwd_mfma_k<NF, KSV, false, CM_UN, true>), dim3(grid), dim3(256), shm, st,          \
                        (const bf16_raw*)x, (const bf16_raw*)w, bias, (bf16_raw*)out, g, act, K, PoolEpi{}, bnacc); \
   else                                                                                                         \
@@ -1206,6 +1243,18 @@ extern "C" int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int*
 #undef HOPSX_CMF_NF
 #undef HOPSX_CMF
   return (int)hipGetLastError();
+}
+
+extern "C" int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int* geom, void* out, const float* bias,
+                                        int act, float* bnacc, hipStream_t st) {
+  return fwd_mfma_impl(x, w, geom, out, bias, act, bnacc, nullptr, st);
+}
+
+// the caller has checked the 16-B alignment of every operand and that res does not overlap out
+extern "C" int hopsx_conv2d_fwd_mfma_res(const void* x, const void* w, const int* geom, void* out, const float* bias,
+                                         int act, const void* res, hipStream_t st) {
+  if (!res || !hopsx_conv_fwd_mfma_ok(geom)) return -2;
+  return fwd_mfma_impl(x, w, geom, out, bias, act, nullptr, res, st);
 }
 
 // conv_fwd_mfma_k IBN: z -> a = act(bn(z)) (stored for the backward) -> conv -> out, with out's BN statistics

@@ -241,6 +241,42 @@ struct EpiStoreBF16 {  // out = act(alpha*acc + bias[n])
   }
 };
 
+// out = act(alpha*acc + bias[n] + res[m, n]): a frozen-inference conv (BatchNorm folded into the weight and
+// the bias) that is the last of its residual block: the shortcut is added before the activation.  res is
+// bf16 with out's layout (row stride ldo) and never aliases out (the launcher refuses that).
+struct EpiStoreResBF16 {
+  static constexpr bool kVec8 = true;
+  bf16_raw* out;
+  long ldo;
+  const float* bias;
+  float alpha;
+  int act;
+  float* colsum;  // always null (kept for the epilogue interface)
+  const bf16_raw* res;
+  __device__ __forceinline__ float operator()(int m, int n, float v) const {
+    v = v * alpha + (bias ? bias[n] : 0.f);
+    v += bf2f(res[(long)m * ldo + n]);
+    v = apply_act(v, act);
+    out[(long)m * ldo + n] = f2bf(v);
+    return v;
+  }
+  __host__ __device__ bool vec8_ok() const {
+    return ldo % 8 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)res % 16 == 0 && !colsum;
+  }
+  // (the gg engine's vectorized epilogue: one 16-B residual load per 8 columns)
+  __device__ __forceinline__ void store8(int m, int n, const float* v) const {
+    const bf16x8 rv = *(const bf16x8*)(res + (long)m * ldo + n);
+    bf16x8 q;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = v[j] * alpha + (bias ? bias[n + j] : 0.f);
+      t += bf2f((uint16_t)rv[j]);
+      q[j] = (short)f2bf(apply_act(t, act));
+    }
+    *(bf16x8*)(out + (long)m * ldo + n) = q;
+  }
+};
+
 // out = bf16(acc) for a conv feeding a training BatchNorm: the column statistics (sum and sum of
 // squares of the stored bf16 values) go to colsum = the replicas [HOPSX_BN_NREP][2N] (kSq)
 struct EpiBnStatsBF16 {
@@ -318,6 +354,18 @@ struct EpiAtomicTicket {
     return v;
   }
 };
+
+// The split-K finish of EpiStoreResBF16 (its own ticket type and epilogue id: the finish of the ids above is
+// compiled without it): fin.add is the residual, fin.bias / alpha / act as kEpiStoreBF16.
+constexpr int kEpiStoreResBF16 = 5;
+struct EpiAtomicTicketRes : EpiAtomicTicket {
+  static constexpr bool kResFinish = true;
+};
+
+template <class EP, class = void>
+struct has_resfin { static constexpr bool value = false; };
+template <class EP>
+struct has_resfin<EP, decltype((void)EP::kResFinish)> { static constexpr bool value = EP::kResFinish; };
 
 template <class EP, class = void>
 struct has_vec8 { static constexpr bool value = false; };
@@ -813,7 +861,12 @@ __device__ __forceinline__ void mfma_gemm_body(const AL& al, const BL& bl, const
       float* wp = ep.out + (long)m * ep.ldo + n;
       float v = *wp;
       *wp = 0.f;
-      if (f.epi == kEpiDActBF16) {
+      if constexpr (has_resfin<EP>::value) {
+        v = v * f.alpha + (f.bias ? f.bias[n] : 0.f);
+        v += bf2f(f.add[(long)m * f.ldo + n]);
+        v = apply_act(v, f.act);
+        ((bf16_raw*)f.out)[(long)m * f.ldo + n] = f2bf(v);
+      } else if (f.epi == kEpiDActBF16) {
         if (f.aux) v *= act_grad_from_out(bf2f(f.aux[(long)m * f.ldaux + n]), f.act);
         if (f.add) v += bf2f(f.add[(long)m * f.ldo + n]);
         ((bf16_raw*)f.out)[(long)m * f.ldo + n] = f2bf(v);

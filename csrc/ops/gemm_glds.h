@@ -798,14 +798,19 @@ inline bool gg_plan(long M, long N, long K, bool allow_split, GgPlan& p, long mi
   return wgs >= min_wg && wgs < (1L << 31);
 }
 
+// launch_gg's own decision, without launching: whether the engine takes the shape, and its plan
+inline bool gg_takes(int M, int N, int K, bool allow_split, GgPlan& p, long min_wg_override = -1) {
+  // deterministic mode keeps gemm_core.h's engine (one K slice per tile, turn-ordered column sums)
+  if (M <= 0 || N <= 0 || K <= 0 || hopsx_disabled("gg") || hopsx_deterministic()) return false;
+  static const bool narrow = !hopsx_disabled("gg_n64");
+  return gg_plan(M, N, K, allow_split, p, min_wg_override, 256, narrow);
+}
+
 template <bool A_KC, bool B_KC, class AS, class BS, class EP>
 inline bool launch_gg(const AS& as, const BS& bs, const EP& ep, int M, int N, int K, bool allow_split,
                       hipStream_t st, long min_wg_override = -1) {
-  // deterministic mode keeps gemm_core.h's engine (one K slice per tile, turn-ordered column sums)
-  if (M <= 0 || N <= 0 || K <= 0 || hopsx_disabled("gg") || hopsx_deterministic()) return false;
   GgPlan p;
-  static const bool narrow = !hopsx_disabled("gg_n64");
-  if (!gg_plan(M, N, K, allow_split, p, min_wg_override, 256, narrow)) return false;
+  if (!gg_takes(M, N, K, allow_split, p, min_wg_override)) return false;
   static const int diag = (int)hopsx_env_int("HOPSX_GG_DIAG", 0);
   const dim3 grid((unsigned)(p.tiles * p.split));
   switch (p.cfg) {

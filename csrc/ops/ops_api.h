@@ -157,6 +157,19 @@ int hopsx_conv2d_fwd_mfma(const void* x, const void* w, const int* geom, void* o
                           hipStream_t st);
 int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
                              float* bnacc, hipStream_t st);
+// Frozen-inference forward: out = act(conv(x, w) + bias[co] + residual[m, co]) (bf16 out; act none or relu), the
+// residual a bf16 tensor of out's layout added before the activation.  hopsx_conv2d_fwd's routing, minus the
+// direct input-layer kernel (which never sees a residual); residual == null IS hopsx_conv2d_fwd (bf16 store).
+// Nothing is launched and an error returned for: an activation other than none / relu (-2), a residual that is
+// not 16-B aligned (-4) or that overlaps out (-5).
+int hopsx_conv2d_fwd_res(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
+                         const void* residual, hipStream_t st);
+// the route hopsx_conv2d_fwd_res takes for this geometry with 16-B aligned operands (the launcher's own
+// decision): 0 direct MFMA kernel (conv_mfma.hip), 1 the gg engine (gemm_glds.h), 2 gemm_core.h's engine,
+// 3 gemm_core.h's engine with split-K and the in-launch ticket finish
+int hopsx_conv2d_fwd_res_path(const int* geom);
+int hopsx_conv2d_fwd_mfma_res(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
+                              const void* res, hipStream_t st);
 // conv forward (bf16 out, no bias / act) whose epilogue also accumulates the BatchNorm statistics
 // of its output into bnacc [HOPSX_BN_NREP][2 CO] (zero at rest; hopsx_bn_fwd_apply_fin consumes and
 // re-zeroes it).  -2: not supported for this shape (nothing launched; use the plain BN path).

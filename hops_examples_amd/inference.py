@@ -11,8 +11,9 @@ worker process per GPU; each worker decodes JPEG/PNG on a thread pool (PIL relea
 runs a :class:`Predictor`: uint8 NHWC batches are packed into pinned host memory and copied to the
 device on a side stream while the previous batch computes (two device input buffers), the forward
 + softmax is replayed from a hipGraph captured once per (batch shape, input buffer) — bf16
-ResNet-50 with batch norm in its inference kernel (running statistics + residual + ReLU in one
-launch) — and each worker writes its shard as Parquet; the driver concatenates the shards.
+ResNet-50 frozen (runtime/frozen.py: batch norm folded into the convs, residual + ReLU in the conv
+epilogue; ``frozen=False``: batch norm in its own inference kernel) — and each worker writes its
+shard as Parquet; the driver concatenates the shards.
 No pretrained ImageNet weights exist offline, so models are random-init unless a checkpoint
 is loaded, and labels default to ``class_<i>`` (pass ``labels=`` for real names).
 """
@@ -67,6 +68,29 @@ def _predict_probs(model, x, device):
         return torch.softmax(logits.float(), dim=-1).cpu().numpy()
 
 
+def _freeze_cpu(frozen):
+    if frozen is True:
+        raise ValueError("frozen=True: the frozen ResNet engine runs on a GPU")
+    if frozen not in ("auto", False, None):
+        raise ValueError(f"frozen: 'auto', True or False, got {frozen!r}")
+    return None
+
+
+def _freeze(model, frozen):
+    """The frozen engine for ``model`` under the ``frozen`` argument of Predictor (see there), or None."""
+    import os
+
+    from .runtime.frozen import FrozenResNet
+
+    if frozen is True:
+        return FrozenResNet.freeze(model)  # (raises for an unsupported model)
+    if frozen == "auto":
+        if os.environ.get("HOPSX_INFER_FROZEN", "1") == "0" or not FrozenResNet.supported(model):
+            return None
+        return FrozenResNet.freeze(model)
+    return _freeze_cpu(frozen)
+
+
 class Predictor:
     """Streaming inference on one device.
 
@@ -74,9 +98,16 @@ class Predictor:
     packed into a pinned host buffer and copied host->device on a side stream while batch i runs;
     the forward (+ softmax) of each (batch shape, input buffer) pair is captured into a hipGraph on
     first use and replayed afterwards (``graph=False``: eager kernels, same results).  On the CPU
-    it is the eager forward."""
+    it is the eager forward.
 
-    def __init__(self, model, device=None, graph: bool = True):
+    ``frozen``: run the hopsx ResNets through :class:`runtime.frozen.FrozenResNet` (BatchNorm folded into
+    the convs, the residual added in the conv epilogue: one launch per conv + BN pair).  ``"auto"`` freezes
+    when the model is supported (a CifarResNet / ResNet50 on a GPU) unless ``HOPSX_INFER_FROZEN=0``;
+    ``True`` insists (an unsupported model is an error); ``False`` keeps ``model.eval()``'s own forward.
+    ``Predictor.frozen`` is the engine or None; it is a snapshot of the model taken here (call its
+    ``refresh()`` after changing the model)."""
+
+    def __init__(self, model, device=None, graph: bool = True, frozen="auto"):
         import torch
 
         self.device = torch.device(device) if device is not None else (
@@ -88,6 +119,7 @@ class Predictor:
         self._bufs: dict = {}    # (shape, dtype) -> ([pinned x2], [device x2])
         self._copy = torch.cuda.Stream(self.device) if self.cuda else None
         self.replays = 0
+        self.frozen = _freeze(self.model, frozen) if self.cuda else _freeze_cpu(frozen)
 
     def _buffers(self, shape, dtype):
         import torch
@@ -102,7 +134,7 @@ class Predictor:
     def _forward(self, t):
         import torch
 
-        return torch.softmax(self.model(t).float(), dim=-1)
+        return torch.softmax((self.frozen or self.model)(t).float(), dim=-1)
 
     def _run(self, dev_in, key):
         import torch
@@ -165,14 +197,16 @@ class Predictor:
                 yield out.cpu().numpy()  # the output buffer is reused two batches later
 
 
-def predict(model, images: np.ndarray, batch_size: int = 64, device=None, graph: bool = True) -> np.ndarray:
-    """Softmax probabilities for uint8 NHWC ``images`` (the hopsx ResNets normalise on device)."""
-    pr = Predictor(model, device, graph=graph)
+def predict(model, images: np.ndarray, batch_size: int = 64, device=None, graph: bool = True,
+            frozen="auto") -> np.ndarray:
+    """Softmax probabilities for uint8 NHWC ``images`` (the hopsx ResNets normalise on device).  ``frozen``: see
+    :class:`Predictor`."""
+    pr = Predictor(model, device, graph=graph, frozen=frozen)
     batches = (images[i:i + batch_size] for i in range(0, len(images), batch_size))
     return np.concatenate(list(pr.predict_batches(batches)))
 
 
-def _shard_worker(model_builder, checkpoint, paths, batch_size, top, labels, out_path, threads):
+def _shard_worker(model_builder, checkpoint, paths, batch_size, top, labels, out_path, threads, frozen="auto"):
     import torch
 
     from .runtime.arena import ParamArena
@@ -210,7 +244,7 @@ def _shard_worker(model_builder, checkpoint, paths, batch_size, top, labels, out
                 order.append([p for p, _ in loaded])
                 yield np.stack([a for _, a in loaded])
 
-    predictor = Predictor(model, dev)
+    predictor = Predictor(model, dev, frozen=frozen)
     for bi, probs in enumerate(predictor.predict_batches(decoded())):
         for p, dec in zip(order[bi], decode_predictions(probs, top, labels)):
             r = {"image_path": str(p)}
@@ -226,9 +260,10 @@ def _shard_worker(model_builder, checkpoint, paths, batch_size, top, labels, out
 
 def batch_predict(model_builder, image_paths: list, output_path: str, batch_size: int = 100, top: int = 3,
                   labels: list[str] | None = None, num_workers: int | None = None, limit: int | None = None,
-                  checkpoint: str | None = None, decode_threads: int = 8, timeout: float | None = None
-                  ) -> pd.DataFrame:
-    """Label ``image_paths`` with one worker process per GPU; writes ``output_path`` (Parquet dir)."""
+                  checkpoint: str | None = None, decode_threads: int = 8, timeout: float | None = None,
+                  frozen="auto") -> pd.DataFrame:
+    """Label ``image_paths`` with one worker process per GPU; writes ``output_path`` (Parquet dir).  ``frozen``:
+    see :class:`Predictor`."""
     from .experiment import _runner as R
 
     paths = list(image_paths)[:limit] if limit else list(image_paths)
@@ -245,7 +280,8 @@ def batch_predict(model_builder, image_paths: list, output_path: str, batch_size
             continue
         w = R.spawn(_shard_worker, {"model_builder": model_builder, "checkpoint": checkpoint, "paths": sh,
                                     "batch_size": batch_size, "top": top, "labels": labels,
-                                    "out_path": str(out / f"part-{i:05d}.parquet"), "threads": decode_threads},
+                                    "out_path": str(out / f"part-{i:05d}.parquet"), "threads": decode_threads,
+                                    "frozen": frozen},
                     out / "_logs", log_name=f"worker_{i}_output.log", gpu=(i % ngpu) if ngpu else None)
         workers.append(w)
     for w in workers:

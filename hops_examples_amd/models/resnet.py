@@ -191,10 +191,12 @@ def _as_nhwc_image(x, m):
         if cout:
             y._hx_chpad = x.shape[-1]  # channels beyond this are zero (nn.Conv2d pads its weight only then)
         return y
-    y = x.float()
+    # (fp32, or fp64 for a model converted with .double(): the fp64 anchor of the inference references)
+    dt = torch.float64 if next(m.parameters()).dtype == torch.float64 else torch.float32
+    y = x.to(dt)
     if m.img_reverse:
         y = y.flip(-1)
-    return y * torch.tensor(m.img_scale_c) + torch.tensor(m.img_shift_c)
+    return y * torch.tensor(m.img_scale_c, dtype=dt) + torch.tensor(m.img_shift_c, dtype=dt)
 
 
 def cifar_resnet(depth: int = 20, num_classes: int = 10) -> CifarResNet:

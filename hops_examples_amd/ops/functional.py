@@ -26,6 +26,12 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 
 
+def _cpu_dtype(w):
+    """Compute dtype of the CPU path: fp32, or fp64 for a model converted with ``.double()`` (the fp64
+    anchor of the inference references)."""
+    return torch.float64 if w is not None and w.dtype == torch.float64 else torch.float32
+
+
 def _cpu_act(y, act):
     a = ACT[act] if not isinstance(act, int) else act
     if a == 1:
@@ -217,7 +223,7 @@ def linear(x, w, b=None, act=None, out_f32=False, drop_in=None):
     if not x.is_cuda:
         if drop_in is not None:
             x = F.dropout(x.float(), drop_in[0], True)
-        return _cpu_act(F.linear(x.float(), w, b), act)
+        return _cpu_act(F.linear(x.to(_cpu_dtype(w)), w, b), act)
     a = ACT[act] if not isinstance(act, int) else act
     xc = to_compute(x)
     src = x if hasattr(x, "_hx_pool") else getattr(x, "_base", None)
@@ -861,7 +867,7 @@ def conv2d(x, w, b=None, stride=1, padding=0, dilation=1, act=None, in_affine=No
         else:
             x = K.u8_normalize(x.contiguous(), float(sc), float(sh))
     if not x.is_cuda:
-        xr = x.float().permute(0, 3, 1, 2)
+        xr = x.to(_cpu_dtype(w)).permute(0, 3, 1, 2)
         if padding == "same" and (w.shape[1] % 2 == 0 or w.shape[2] % 2 == 0):
             # TF 'same' pads the extra row/col at the end for even kernels
             th, tw = dl[0] * (w.shape[1] - 1), dl[1] * (w.shape[2] - 1)
@@ -1126,7 +1132,8 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training=True, momentu
     a = ACT[act] if not isinstance(act, int) else act
     C = x.shape[-1]
     if not x.is_cuda:
-        y = F.batch_norm(x.reshape(-1, C).float(), running_mean, running_var, gamma, beta, training, momentum, eps)
+        y = F.batch_norm(x.reshape(-1, C).to(_cpu_dtype(running_mean)), running_mean, running_var, gamma, beta,
+                         training, momentum, eps)
         y = y.view(x.shape)
         if residual is not None:
             y = y + residual

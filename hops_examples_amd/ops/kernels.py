@@ -201,6 +201,49 @@ def conv2d_fwd(x, w, geom, bias=None, act=0, out=None, colsum=None, in_affine=No
     return out
 
 
+_RES_ROUTES = ("mfma", "gg", "gemm", "splitk")
+
+
+def conv2d_fwd_res(x, w, geom, bias=None, act=0, residual=None, out=None):
+    """out = act(conv(x, w) + bias + residual), bf16: the frozen-inference forward (BatchNorm folded into
+    ``w`` / ``bias``) with the block's shortcut added in the conv epilogue, before the activation (none or
+    relu).  ``residual``: bf16, the output's shape, 16-B aligned, not overlapping ``out`` — anything else is
+    refused, never worked around.  ``residual=None`` is ``conv2d_fwd`` itself."""
+    if residual is None:
+        return conv2d_fwd(x, w, geom, bias=bias, act=act, out=out)
+    _req(x, BF16, "x")
+    _req(w, BF16, "w")
+    _req(residual, BF16, "residual")
+    B, OH, OW, CO = geom[0], geom[4], geom[5], geom[6]
+    if residual.numel() != B * OH * OW * CO or residual.shape[-1] != CO:
+        raise ValueError(f"residual: expected the output's shape {(B, OH, OW, CO)}, got {tuple(residual.shape)}")
+    if act_id(act) not in (0, 1):
+        raise ValueError("conv2d_fwd_res: the activation is none or relu")
+    if out is None:
+        out = torch.empty(B, OH, OW, CO, device=x.device, dtype=BF16)
+    _req(out, BF16, "out")
+    if bias is not None:
+        _req(bias, F32, "bias")
+    if residual.data_ptr() % 16:
+        raise ValueError("conv2d_fwd_res: the residual must be 16-byte aligned")
+    nb = out.numel() * 2
+    if residual.data_ptr() < out.data_ptr() + nb and out.data_ptr() < residual.data_ptr() + nb:
+        raise ValueError("conv2d_fwd_res: the residual must not alias the output")
+    check(_C.ext().conv2d_fwd_res(ptr(x), ptr(w), list(geom), ptr(out), ptr(bias), act_id(act), ptr(residual),
+                                  stream()), "conv2d_fwd_res")
+    return out
+
+
+def conv2d_fwd_res_path(geom) -> str:
+    """The route conv2d_fwd_res takes for this geometry (the launcher's own decision, csrc/ops/conv.hip
+    hopsx_conv2d_fwd_res_path): 'mfma' the direct MFMA kernel, 'gg' the LDS-DMA tile engine, 'gemm' the
+    register-staged engine, 'splitk' that engine with split-K and the in-launch finish."""
+    geom = [int(v) for v in geom]
+    if len(geom) != 15:
+        raise ValueError("conv2d_fwd_res_path: geom is the 15-entry vector of conv_geom")
+    return _RES_ROUTES[_C.ext().conv2d_fwd_res_path(geom)]
+
+
 def conv_fwd_pool_ok(geom, act, pk: int = 2) -> bool:
     """conv(geom, act) -> pk x pk / stride-pk max-pool (pk 2 or 4, floor windows) can run as one launch
     (conv_mfma.hip POOL epilogue)."""

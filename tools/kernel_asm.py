@@ -5,7 +5,15 @@ drops comments and .loc / .file lines, and prints `identical` or `DIFFERENT (n l
 differing lines.  Exits non-zero on any difference.  It compares texts; it looks for no particular instruction.
 A refactor that only moves definitions must leave every kernel identical.
 
-usage: python tools/kernel_asm.py [--base REV] [--show N] [FILE.hip ...]"""
+`--normalize`, for a change that ADDS template instantiations or a trailing template flag to a kernel:
+  * function-local labels `.LBB<n>_<m>` carry the number of the function within its file, which moves when
+    instantiations are added before it: they are compared as `.LBB_<m>`;
+  * a kernel of the base that is missing from the working tree is paired with the tree's kernel of the same
+    template whose arguments are the base's plus one trailing `false` (a new flag, off); the pair is compared
+    as one kernel and named `A == B`.  Whatever else differs (a longer argument list: kernarg size, offsets of
+    the hidden arguments) is still reported line by line.
+
+usage: python tools/kernel_asm.py [--base REV] [--show N] [--normalize] [FILE.hip ...]"""
 import argparse
 import concurrent.futures as cf
 import difflib
@@ -56,8 +64,36 @@ def kernels(asm):
 
 def demangled(names):
     r = subprocess.run(["c++filt"], input="\n".join(names), stdout=subprocess.PIPE, text=True)
-    short = [re.sub(r"\(.*", "", s) for s in r.stdout.split("\n")]
+    short = [re.sub(r"\((?!anonymous namespace).*", "", s) for s in r.stdout.split("\n")]
     return dict(zip(names, short)) if r.returncode == 0 and len(short) >= len(names) else {n: n for n in names}
+
+
+def unlabel(lines):
+    return [re.sub(r"\.LBB\d+_", ".LBB_", ln) for ln in lines]
+
+
+def pair_trailing_flag(base, tree):
+    """Renames tree kernels `k<args, false>` to the base symbol `k<args>` that the tree no longer has; returns
+    {base symbol: tree symbol} of the pairs made."""
+    gone = [s for s in base if s not in tree]
+    new = [s for s in tree if s not in base]
+    full = lambda names: dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), stdout=subprocess.PIPE,
+                                                        text=True).stdout.split("\n")))
+    dg, dn = full(gone), full(new)
+    tmpl = lambda d: re.match(r"(.*?<)(.*)(>\(.*)", d)  # (head<, template args, >(parameters...)
+    by_args = {}
+    for s in new:
+        m = tmpl(dn.get(s, ""))
+        if m and m.group(2).endswith(", false"):
+            by_args[m.group(1) + m.group(2)[:-len(", false")]] = s
+    pairs = {}
+    for s in gone:
+        m = tmpl(dg.get(s, ""))
+        t = by_args.get(m.group(1) + m.group(2)) if m else None
+        if t is not None:
+            pairs[s] = t
+            tree[s] = [ln.replace(t, s) for ln in tree.pop(t)]
+    return pairs
 
 
 def base_tree(rev, into):
@@ -74,6 +110,8 @@ def main():
     ap.add_argument("files", nargs="*", default=DEFAULT, help="file names under csrc/ops")
     ap.add_argument("--base", default="HEAD", help="revision to compare the working tree against")
     ap.add_argument("--show", type=int, default=6, help="differing lines printed per kernel")
+    ap.add_argument("--normalize", action="store_true", help="ignore label numbering, pair kernels that gained a "
+                    "trailing template flag (see above)")
     a = ap.parse_args()
     bad = 0
     with tempfile.TemporaryDirectory() as d:
@@ -91,10 +129,14 @@ def main():
                 fut, out = jobs[f, side]
                 fut.result()
                 texts[side] = kernels(open(out).read())
+            pairs = pair_trailing_flag(texts["base"], texts["tree"]) if a.normalize else {}
             names = demangled(sorted(set(texts["base"]) | set(texts["tree"])))
-            print(f"== {f}  ({a.base} -> working tree)")
+            print(f"== {f}  ({a.base} -> working tree)" + (f"  [normalized; {len(pairs)} kernels paired with their "
+                                                            "<..., false> successor]" if a.normalize else ""))
             for sym, nice in names.items():
                 b, t = texts["base"].get(sym), texts["tree"].get(sym)
+                if a.normalize and b is not None and t is not None:
+                    b, t = unlabel(b), unlabel(t)
                 if b is None or t is None:
                     bad += 1
                     print(f"  {nice:<64} only in the {'working tree' if b is None else 'base'}")
