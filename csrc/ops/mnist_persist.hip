@@ -94,6 +94,16 @@ constexpr int D_BYTES = D_F32 + (NCONV - OFF_B2) * 4;
 constexpr int TGB_N = NHEAD * (HID / 2);  // 2048 granules (16 KB) per parity
 constexpr int TG_WORDS = 2 * 2 * TGB_N;   // 32-bit words of the tag region
 static_assert(FL_WORDS % 2 == 0 && TGB_N % 256 == 0, "granules are 8-B aligned; every thread owns TGB_N / 256");
+// Waits filled with work that is ready early and needs nothing from the hand-off waited for (HOPSX_PERSIST_FILL, one
+// bit per part, in Args::hand).  No float operation changes its operands or its order: only where it runs
+constexpr int HAND_FILL_C = 1 << 16;     // owners of <false>: the fc1 slice Adadelta, a chunk per poll of the C gather
+constexpr int HAND_FILL_KEEP = 1 << 17;  // the next step's dropout keep mask drawn in the B wait
+constexpr int HAND_FMAX_SHIFT = 20;      // 4 bits: chunks that may run inside the C wait (HOPSX_PERSIST_FILL_MAX)
+// the 32 lane-owned fc1 updates of a step in chunks of FCH, in the order of the whole update (ii, j, r).  A chunk has
+// to stay well below a flag round trip (it runs between a poll's loads and the ballot that consumes them): 4 updates
+// are ~60 VALU, 8 of them quarter-rate (sqrt, rsq)
+constexpr int FCH = 4, NFCH = 32 / FCH;
+static_assert(32 % FCH == 0 && NFCH <= 15, "whole chunks; the cap fits its 4 bits of Args::hand");
 
 // LDS row strides (bf16 elements) of the backward-only images, by mnist_cnn.h's rule
 constexpr int DHS = row_stride(HID), DCS = row_stride(4 * B);
@@ -192,8 +202,10 @@ struct Args {
   // hand-off form, one word (one scalar register for the whole launch): bit 0: the positions read dh (B) from
   // tagged granules, not the flag form (HOPSX_PERSIST_TAGGED); bit 1: a flag poll loads the error word with
   // its flags, one round trip (HOPSX_PERSIST_POLL1); bit 3: the slice owners load a partial of C as soon as its
-  // flag is there (HOPSX_PERSIST_PROG bit 1); bits 8..: heads whose tag opens the B wait's gate
-  // (HOPSX_PERSIST_GATE)
+  // flag is there (HOPSX_PERSIST_PROG bit 1); bits 8..15: heads whose tag opens the B wait's gate
+  // (HOPSX_PERSIST_GATE); bits 16..17: the waits that are filled with work that is ready early
+  // (HOPSX_PERSIST_FILL, HAND_FILL_*); bits 20..23: chunks of the fc1 update the owners may run inside the C wait
+  // (HOPSX_PERSIST_FILL_MAX)
   int hand;
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
   // data parallel (DP instantiation)
@@ -466,13 +478,20 @@ __device__ __forceinline__ bool sweep_tags(const unsigned long long* g, int tid,
 // OWN poll has shown that producer's flag; no wave relies on another's poll.  Failure handling as sweep_tags: every
 // poll is bounded by `tmo` (recording `code`) and watches the sticky error word; a wave that gives up sets *s_fail.
 // No barrier in here: the caller reads *s_fail (uniform) behind the barrier that follows its reduce.
-template <int NK, class L>
+// fill(): work of the caller's that is ready and needs nothing from the hand-off, run between issuing a poll's two
+// loads and the ballot that consumes them, i.e. inside the round trip the wave would otherwise sit out; it returns
+// whether it did anything (wave-uniform), and a poll whose fill did takes no s_sleep.  It must stay shorter than a
+// flag round trip (or the last flag is seen late) and must not touch what load() writes.
+template <int NK, class L, class F>
 __device__ __forceinline__ void gather_rows(const unsigned* flag, bool mine, int shift, unsigned pend, unsigned epoch,
-                                            unsigned* err, unsigned code, int* s_fail, long long tmo, L load) {
+                                            unsigned* err, unsigned code, int* s_fail, long long tmo, L load, F fill) {
   const long long t0 = wall_clock64();
   for (unsigned spins = 0;; ++spins) {
     const unsigned e = flag_load(err);
     const unsigned f = mine ? flag_load(flag) : 0u;
+    __builtin_amdgcn_sched_barrier(0);  // (the loads are issued ahead of the fill, their wait stays behind it)
+    const bool filled = fill();
+    __builtin_amdgcn_sched_barrier(0);
     const unsigned long long here = __ballot(mine && f == epoch);
     const unsigned now = pend & (unsigned)(here >> shift);
 #pragma unroll
@@ -489,7 +508,7 @@ __device__ __forceinline__ void gather_rows(const unsigned* flag, bool mine, int
       if ((threadIdx.x & 63) == 0) *s_fail = 1;
       break;
     }
-    __builtin_amdgcn_s_sleep(1);
+    if (!filled) __builtin_amdgcn_s_sleep(1);
   }
 }
 
@@ -580,8 +599,9 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
   const float P = a.drop_p, inv = P > 0.f ? 1.f / (1.f - P) : 1.f;
   unsigned char* KEEP = smem + L_KEEP;
   // the dropout keep mask of step s for this position (common.h drop_key / uniform01 on the NHWC
-  // index of the pooled element): it depends only on the step, so it is drawn while the previous
-  // step waits for its D hand-off, off the critical path
+  // index of the pooled element): it depends only on the step and KEEP is read by the conv2 forward epilogue
+  // alone, so it is drawn while the previous step waits for B, where the positions idle (HAND_FILL_KEEP; without
+  // it behind the previous step's fc1 update, where the owners have no slack left)
   auto draw_keep = [&](int s) {
     const unsigned long long ctr = ctr0 + (unsigned long long)s;
     const uint64_t dkey = (uint64_t)seed ^ ((uint64_t)a.salt * 0xD1B54A32D192ED03ull) ^
@@ -773,6 +793,9 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     }
     if (s + 1 < a.nsteps) xv = xload(s + 1);  // next step's patch, consumed next iteration
     stamp(a, s, 2);
+    // the next step's keep mask, at the head of the B wait: the heads need ~6 us from here, and KEEP was last read
+    // by this step's conv2 epilogue, two barriers back
+    if ((a.hand & HAND_FILL_KEEP) && s + 1 < a.nsteps) draw_keep(s + 1);
     // ---- B: dh of all 32 images ----
     // (step 0: the heads run on this GPU only, so a B that has not come within tmo0 means workgroups of
     // this launch are not resident — fail fast with the co-residency code instead of waiting out tmo)
@@ -783,7 +806,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       const unsigned long long* TB = (const unsigned long long*)(a.flags + FL_WORDS) + par * TGB_N;
       const unsigned code = s ? ecode(2, s) : ecode(12, 0);
       const long long tmo = s ? a.tmo : a.tmo0;
-      if (!gate_tags(TB, p & (HID / 2 - 1), ep, (a.hand >> 8), a.err, code, s_ok, tmo)) return;
+      if (!gate_tags(TB, p & (HID / 2 - 1), ep, (a.hand >> 8) & 0xFF, a.err, code, s_ok, tmo)) return;
       if (!sweep_tags<TGB_N / 256>(TB, tid, ep, a.err, code, s_ok + 2, tmo, [&](int idx, unsigned v) {
             *(unsigned*)(DH + (idx >> 6) * DHS + 2 * (idx & 63)) = v;
           }))
@@ -818,6 +841,19 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     }
     // ---- fc1 input gradient ----
     f32x4 gw[2][4], dp[2];
+    // The fc1 slice update (Adadelta on the lane-owned registers, new bf16 weights for the next forward) in NFCH
+    // chunks, c static: chunk c is elements c FCH .. c FCH + FCH - 1 of the whole update's order (ii, j, r).  fleft
+    // (wave-uniform) holds the chunks not yet run this step: each runs exactly once, inside the owners' C wait or,
+    // whatever is left, where the whole update has always run, behind the D publish
+    auto fc1_chunk = [&](int c) {
+#pragma unroll
+      for (int q = 0; q < FCH; ++q) {
+        const int el = c * FCH + q, ii = el >> 4, j = (el >> 2) & 3, r = el & 3;
+        wm[ii][j][r] = adadelta(wm[ii][j][r], gw[ii][j][r] * hp.gscale, g1[ii][j][r], g2[ii][j][r], hp);
+        W1[((2 * w + ii) * 16 + fq * 4 + r) * W1S + j * 16 + fr] = f2bf_hw(wm[ii][j][r]);
+      }
+    };
+    unsigned fleft = (1u << NFCH) - 1u;
     unsigned char amv[2][4];  // the pool backward's argmax bytes, read with the fragments
     {
       // every fragment and the 8 argmax bytes in flight before the first MFMA
@@ -1057,7 +1093,23 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         // (lq = 3) bits 36 .. 44 follow as its rows 9 .. 17
         const int lp = lane < 4 * NKC ? 4 * w + lane / NKC + NRED * (lane % NKC) : gx + NRED * (lane - 4 * NKC);
         const bool mine = lane < 4 * NKC || (gx < NRED && lane < 5 * NKC && lp < NPOS);
-        gather_rows<2 * NKC>(a.flags + FL_C + lp, mine, lq * NKC, pend, ep, a.err, ecode(3, s), s_ok + 2, a.tmo, load);
+        // the fill (HAND_FILL_C, <false> only: the data-parallel weight gradient does not exist yet): this wave's
+        // next chunk of the fc1 update per poll, up to the cap; the chunk index selects among statically indexed
+        // copies (the pend-mask idiom), so wm / g1 / g2 / gw stay in registers
+        int fcap = !DP && (a.hand & HAND_FILL_C) ? (a.hand >> HAND_FMAX_SHIFT) & 15 : 0;
+        auto fill = [&]() -> bool {
+          if (fcap <= 0) return false;
+          // (fcap <= NFCH: a chunk is left; wave-uniform, and told so: scalar branches around the copies)
+          const unsigned bit = __builtin_amdgcn_readfirstlane(fleft & (0u - fleft));
+#pragma unroll
+          for (int c = 0; c < NFCH; ++c)
+            if ((bit >> c) & 1u) fc1_chunk(c);
+          fleft &= ~bit;
+          --fcap;
+          return true;
+        };
+        gather_rows<2 * NKC>(a.flags + FL_C + lp, mine, lq * NKC, pend, ep, a.err, ecode(3, s), s_ok + 2, a.tmo, load,
+                             fill);
         stamp(a, s, 7);  // (the partials' load is inside the wait in this form)
       } else {
         lost = !wait_all(a.flags + FL_C, NPOS, ep, a.err, ecode(3, s), a.acquire, s_ok, a.tmo, a.pollw_c, a.stagger,
@@ -1202,17 +1254,13 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       }
     }
     // ---- Adadelta on the fc1 slice (registers) and the new bf16 weights for the next forward: off the
-    // critical path, while this workgroup waits for the D hand-off (W1 is next read after it) ----
+    // critical path, while this workgroup waits for the D hand-off (W1 is next read after it).  The owners of
+    // <false> have run some or all of its chunks inside their C wait: here whatever is left ----
 #pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          wm[ii][j][r] = adadelta(wm[ii][j][r], gw[ii][j][r] * hp.gscale, g1[ii][j][r], g2[ii][j][r], hp);
-          W1[((2 * w + ii) * 16 + fq * 4 + r) * W1S + j * 16 + fr] = f2bf_hw(wm[ii][j][r]);
-        }
-    if (s + 1 < a.nsteps) draw_keep(s + 1);  // KEEP is next read after the D wait's barrier
+    for (int c = 0; c < NFCH; ++c)
+      if ((__builtin_amdgcn_readfirstlane(fleft) >> c) & 1u) fc1_chunk(c);
+    // (KEEP is next read after the D wait's barrier)
+    if (!(a.hand & HAND_FILL_KEEP) && s + 1 < a.nsteps) draw_keep(s + 1);
     stamp(a, s, 9);
     // ---- D: the updated conv parameters for the next step ----
     if (!owner && tid < 64) {
@@ -1702,7 +1750,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.tmo0 = a.tmo;
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
-  static int kn_tagged, kn_gate, kn_poll1, kn_prog;
+  static int kn_tagged, kn_gate, kn_poll1, kn_prog, kn_fill, kn_fmax;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1744,6 +1792,15 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     // one HOPSX_PERSIST_POLLW_C still acts on.  Bit 0 was the heads' A rows: measured slower, not in the tree,
     // ignored (so 3, the default, is 2 and 1 is 0)
     kn_prog = (int)(hopsx_env_int("HOPSX_PERSIST_PROG", 3) & 2);
+    // waits filled with work that is ready early (position_wg; profiles/r17_persist_fill_waits.txt), one bit per
+    // part, default all: 1 the owners' fc1 slice Adadelta inside the progressive C gather (<false>, needs _PROG),
+    // 2 the next step's dropout mask drawn in the B wait.  _FILL_MAX caps the chunks (of FCH fc1 updates, NFCH in
+    // all) that part 1 runs inside the wait — how many fit depends on timing otherwise; 0 is the old placement
+    // through the new path.  No bit and no cap changes a result.  bench.py +4 % with both; 8 updates a chunk and
+    // a third part (D's conv2 weights held in registers over the next step's conv1) measured no gain: not in the tree
+    kn_fill = (int)(hopsx_env_int("HOPSX_PERSIST_FILL", 3) & 3);
+    const long fm = hopsx_env_int("HOPSX_PERSIST_FILL_MAX", NFCH);
+    kn_fmax = (int)(fm >= 0 && fm <= NFCH ? fm : NFCH);
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1754,7 +1811,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.pollw_c = kn_c;
   a.pollw_d = kn_d;
   a.head1w = kn_head1w;
-  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8);
+  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8) | (kn_fill << 16) | (kn_fmax << HAND_FMAX_SHIFT);
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;
   a.inv_gb = 1.f / (float)(world * B);
   if (dp) {
@@ -1838,4 +1895,5 @@ extern "C" void hopsx_mnist_persist_geom(long* g) {
   g[20] = XO_CONV;
   g[21] = XS_CONV;
   g[22] = TG_WORDS;  // tag granules of hand-off B behind the flag rows (32-bit words)
+  g[23] = NFCH;      // chunks of the fc1 slice update (the range of HOPSX_PERSIST_FILL_MAX)
 }

@@ -54,7 +54,8 @@ def geometry() -> dict:
         g = _ext().mnist_persist_geom()
         _GEOM = dict(zip(["batch", "npos", "nhead", "grid", "nconv", "nslice", "slice", "pay", "flag_words",
                           "lds_bytes", "d_bytes", "x_bytes", "xflag_words", "max_ranks", "xo_pool", "xs_pool",
-                          "xo_dht", "xs_dht", "xo_fc2", "xs_fc2", "xo_conv", "xs_conv", "tag_words"], g))
+                          "xo_dht", "xs_dht", "xo_fc2", "xs_fc2", "xo_conv", "xs_conv", "tag_words", "fill_chunks"],
+                         g))
     return _GEOM
 
 

@@ -103,6 +103,10 @@ def timing(n, reps=5, loopback=0):
     # with HOPSX_PERSIST_PROG=0 they mean what they say.  (A, "last A publish -> A ready" / "head compute", is
     # in the flag form either way)
 
+    # With HOPSX_PERSIST_FILL bit 1 (the default) the owners of <false> run chunks of their fc1 slice Adadelta inside
+    # "owner: wait C", one per poll: "owner: fc1 slice Adadelta" is what was left over when the wait ended.  With bit
+    # 2 the next step's dropout mask is drawn at the head of "wait B (heads)" and no longer closes "owner: fc1 slice
+    # Adadelta" (which is a row of the owners alone: the other positions' update + draw end at stamp 9 much earlier)
     rows = [("conv fwd (input, conv1, conv2 MFMA, pool, dropout)", pos, 0, 1), ("fc1 partial + publish A", pos, 1, 2),
             ("wait B (heads)", pos, 2, 3), ("dh load + fc1 wgrad/dgrad + pool bwd", pos, 3, 4),
             ("conv2 wgrad/dgrad + conv1 wgrad", pos, 4, 5), ("publish C", pos, 5, 6),
