@@ -192,6 +192,9 @@ HX_PYMOD(HOPSX_MODNAME) {
   m.def("taxi_eval_bins", []() { return hopsx_taxi_eval_bins(); });
   m.def("mnist_persist_reload_knobs", []() { hopsx_mnist_persist_reload_knobs(); });
   m.def("mnist_persist_occupancy", [](int dp) { return hopsx_mnist_persist_occupancy(dp); });
+  m.def("wave_sum_probe", [](u x, long rows, u out_ref, u out_tree, u st) {
+    return hopsx_wave_sum_probe(P<float>(x), rows, P<float>(out_ref), P<float>(out_tree), S(st));
+  });
   m.def("pad_cin", [](u w, long R, int C, int cp, u out, u out16, u st) {
     return hopsx_pad_cin(P<float>(w), R, C, cp, P<float>(out), P<void>(out16), S(st));
   });

@@ -59,6 +59,35 @@ __device__ __forceinline__ float row_fold(float v) {
   return v;
 }
 
+// wave_sum with the same pairing tree, hence the same bits in every lane, and no LDS round trip (wave_sum's six
+// __shfl_xor are six dependent ds_bpermute).  The xor-32 and xor-16 steps are lane swaps (v_permlane32_swap /
+// v_permlane16_swap exchange the upper half / the odd rows of one operand with the lower half / the even rows of the
+// other: with both operands v, the two results added are v[l] + v[l ^ 32] resp. v[l] + v[l ^ 16], for the swapped
+// lanes with the operands exchanged, and IEEE addition is commutative bit for bit, NaN payloads aside).  After the
+// 16-step the lanes of a 16-lane row hold values of period 16 in the lane index, after the 8-step of period 8, and so
+// on: rotating by o inside the row reads the same operand as xor o, so the xor 8, 4, 2, 1 steps are DPP row
+// rotations — in THAT order only (ascending, the row_fold order, pairs other operands and rounds differently)
+__device__ __forceinline__ float wave_sum_tree(float v) {
+  // (inline assembly: through __builtin_amdgcn_permlane32_swap / 16_swap this compiler adds the first result to
+  // itself, `v_add_f32 v4, v4, v4` behind the swap, whether or not it can see that both operands are equal — the probe
+  // then differs from wave_sum in every finite row.  The compiler's hazard recognizer does not see into the string, so
+  // the wait states are in it.  `s_nop 1` in front: a VALU write of either operand needs 2 wait states before the
+  // swap reads it (LLVM's gfx950 hazard rule for v_permlane*_swap; hipcc's own code for the builtin has
+  // exactly `v_mov_b32 / s_nop 1 / v_permlane32_swap`).  `s_nop 0` behind: no rule asks for it — the
+  // same compiler output puts the dependent v_add directly behind the swap — it is margin of one cycle per swap)
+  float a0 = v, a1 = v;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a0), "+v"(a1));
+  v = a0 + a1;
+  float b0 = v, b1 = v;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 0" : "+v"(b0), "+v"(b1));
+  v = b0 + b1;
+  v += dpp_ror<8>(v);
+  v += dpp_ror<4>(v);
+  v += dpp_ror<2>(v);
+  v += dpp_ror<1>(v);
+  return v;
+}
+
 // Grid-wide "am I the last workgroup?" for a launch whose workgroups each arrive once (thread 0
 // calls it after the workgroup's writes are complete and released).  The counter is 9 x 32 uint32,
 // zero at rest: 8 shards on their own 128-B lines (blockIdx % 8 = the XCD under round-robin

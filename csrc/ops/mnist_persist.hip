@@ -99,6 +99,12 @@ static_assert(FL_WORDS % 2 == 0 && TGB_N % 256 == 0, "granules are 8-B aligned; 
 constexpr int HAND_FILL_C = 1 << 16;     // owners of <false>: the fc1 slice Adadelta, a chunk per poll of the C gather
 constexpr int HAND_FILL_KEEP = 1 << 17;  // the next step's dropout keep mask drawn in the B wait
 constexpr int HAND_FMAX_SHIFT = 20;      // 4 bits: chunks that may run inside the C wait (HOPSX_PERSIST_FILL_MAX)
+// The heads' A-to-B chain (head_wg; profiles/r18_persist_head_chain.txt).  Like the fills, nothing here changes a
+// float operation's operands or order, and no producer, payload, flag, epoch or granule
+constexpr int HAND_GATEA_SHIFT = 18;     // 2 bits: the one-line gate in front of the heads' A wait (HOPSX_PERSIST_GATE_A)
+constexpr int HAND_HEAD_REGS = 1 << 24;  // the one-wave head's operands in registers from the top of the step
+constexpr int HAND_HEAD_TREE = 1 << 25;  // its ten logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN bits 1, 2)
+constexpr int NLINE_A = (NPOS + 31) / 32;  // 128-byte lines of the A flag row
 // the 32 lane-owned fc1 updates of a step in chunks of FCH, in the order of the whole update (ii, j, r).  A chunk has
 // to stay well below a flag round trip (it runs between a poll's loads and the ballot that consumes them): 4 updates
 // are ~60 VALU, 8 of them quarter-rate (sqrt, rsq)
@@ -205,8 +211,10 @@ struct Args {
   // flag is there (HOPSX_PERSIST_PROG bit 1); bits 8..15: heads whose tag opens the B wait's gate
   // (HOPSX_PERSIST_GATE); bits 16..17: the waits that are filled with work that is ready early
   // (HOPSX_PERSIST_FILL, HAND_FILL_*); bits 20..23: chunks of the fc1 update the owners may run inside the C wait
-  // (HOPSX_PERSIST_FILL_MAX)
+  // (HOPSX_PERSIST_FILL_MAX); bits 18..19: the gate in front of the heads' A wait (HOPSX_PERSIST_GATE_A); bits 24..25:
+  // the one-wave head's operands in registers, its logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN, HAND_HEAD_*)
   int hand;
+  int gate_a_tk;  // wall-clock ticks the A gate watches its line before it gives way to the full wait (_GATE_A_US)
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
   // data parallel (DP instantiation)
   int world, rank;
@@ -1398,7 +1406,48 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
     const unsigned ep = (unsigned)(eb + (unsigned long long)s + 1ull);
     const int par = s & 1;
     const int y = (int)a.ys[((cur0 + s) % a.nbatch) * B + i];
+    // The one-wave head's operands: lane l's two fc1 biases, its two columns of the fc2 weight, the ten fc2 biases.
+    // They are stable from the barrier that closes the previous step's fc2 update (step 0: the prologue's) to this
+    // step's update, so with HAND_HEAD_REGS they are read here, where the head waits for A anyway, and not inside
+    // the chain from the last A flag to the granule store that releases the positions; the dh loop reads the
+    // same registers.  (Opaque to the compiler behind the read, or it re-reads LDS at the use)
+    float rb1[2], rw[NCLS][2], rb2[NCLS];
+    auto head_operands = [&]() {
+      const int n0 = 2 * lane;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) rb1[u] = HB1[n0 + u];
+#pragma unroll
+      for (int c = 0; c < NCLS; ++c) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) rw[c][u] = HW[c * HID + n0 + u];
+        rb2[c] = HB2[c];
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) asm volatile("" : "+v"(rb1[u]));
+#pragma unroll
+      for (int c = 0; c < NCLS; ++c) asm volatile("" : "+v"(rw[c][0]), "+v"(rw[c][1]), "+v"(rb2[c]));
+    };
+    if (tid < 64 && a.head1w && (a.hand & HAND_HEAD_REGS)) head_operands();  // (wave 0 alone computes the head)
     // ---- A: reduce the 169 fc1 partial rows of image i (fixed order) ----
+    // On one GPU a head gets here ~9 us before the last position publishes A, and 32 heads polling all NLINE_A
+    // flag lines at s_sleep(1) cadence all that time sit on the lines the 169 producers store their flags into (the
+    // pattern that delayed the owners' D flag stores: the non-owners' gate at the end of position_wg).  So wave 0
+    // first watches ONE line, a lane per flag, at a slow cadence, until the whole line carries the epoch
+    // (HOPSX_PERSIST_GATE_A: 1 head i line i % NLINE_A, ~5 slow pollers a line; 2 every head line 0).  The gate
+    // only delays the wait below, which checks every flag, the error word and the timeout as before; it is bounded
+    // by time alone (gate_a_tk, also in step 0: a grid that is not co-resident fails gate_a_tk + tmo0 after entry).
+    // It holds back wave 0 only: with HOPSX_PERSIST_POLLW_A > 1 the other polling waves enter the wait below at once
+    // and poll every line at the fast cadence, so an A/B of POLLW_A measures the gate only at 1 (the default)
+    if (const int ga = (a.hand >> HAND_GATEA_SHIFT) & 3; ga && tid < 64) {
+      const int l0 = ga == 1 ? (i % NLINE_A) * 32 : 0;
+      const bool mine = lane < 32 && l0 + lane < NPOS;
+      const long long t0 = wall_clock64();
+      for (;;) {
+        const unsigned f = mine ? flag_load(a.flags + FL_A + l0 + lane) : ep;
+        if (__all(f == ep) || wall_clock64() - t0 >= a.gate_a_tk) break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+    }
     if (!wait_all(a.flags + FL_A, NPOS, ep, a.err, s ? ecode(1, s) : ecode(12, 0), a.acquire, s_ok,
                   s ? a.tmo : a.tmo0, a.pollw_a, a.stagger, (a.hand & 2)))
       return;
@@ -1427,18 +1476,24 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
       // round trip) — four barriers and three LDS passes off the critical A -> B chain
       if (tid < 64) {
         const int n0 = 2 * lane;
+        if (!(a.hand & HAND_HEAD_REGS)) head_operands();
         float h[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           float v = 0.f;
 #pragma unroll
           for (int g = 0; g < 8; ++g) v += RED[g * HID + n0 + u];
-          h[u] = fmaxf(v + HB1[n0 + u], 0.f);
+          h[u] = fmaxf(v + rb1[u], 0.f);
         }
+        // the ten logits: wave_sum_tree is wave_sum's pairing tree (the same bits) without its 6 LDS round trips
         float z[NCLS];
+        if (a.hand & HAND_HEAD_TREE) {
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c)
-          z[c] = wave_sum(fmaf(h[1], HW[c * HID + n0 + 1], h[0] * HW[c * HID + n0])) + HB2[c];
+          for (int c = 0; c < NCLS; ++c) z[c] = wave_sum_tree(fmaf(h[1], rw[c][1], h[0] * rw[c][0])) + rb2[c];
+        } else {
+#pragma unroll
+          for (int c = 0; c < NCLS; ++c) z[c] = wave_sum(fmaf(h[1], rw[c][1], h[0] * rw[c][0])) + rb2[c];
+        }
         float m = z[0];
 #pragma unroll
         for (int c = 1; c < NCLS; ++c) m = fmaxf(m, z[c]);
@@ -1461,7 +1516,7 @@ __device__ __forceinline__ void head_wg(const Args& a, unsigned char* smem, int*
         for (int u = 0; u < 2; ++u) {
           float d = 0.f;
 #pragma unroll
-          for (int c = 0; c < NCLS; ++c) d = fmaf(dl[c], HW[c * HID + n0 + u], d);
+          for (int c = 0; c < NCLS; ++c) d = fmaf(dl[c], rw[c][u], d);
           dh[u] = h[u] > 0.f ? d : 0.f;
         }
         // the tagged dh first (what the positions wait for): one 8-byte write-through store per lane, no drain
@@ -1751,6 +1806,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
   static int kn_tagged, kn_gate, kn_poll1, kn_prog, kn_fill, kn_fmax;
+  static int kn_gate_a, kn_gate_a_tk, kn_head;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1801,6 +1857,20 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     kn_fill = (int)(hopsx_env_int("HOPSX_PERSIST_FILL", 3) & 3);
     const long fm = hopsx_env_int("HOPSX_PERSIST_FILL_MAX", NFCH);
     kn_fmax = (int)(fm >= 0 && fm <= NFCH ? fm : NFCH);
+    // the heads' A-to-B chain (head_wg; profiles/r18_persist_head_chain.txt).  _GATE_A: the one-line gate in front
+    // of the A wait, 0 none, 1 head i on line i % 6, 2 every head on line 0 (one process, 12 alternated reps:
+    // 21.77 / 21.49 / 22.30 us/step for 0 / 1 / 2: 1 is the default; 32 pollers on ONE line are worse than none).
+    // _GATE_A_US: how long the gate watches before the full wait takes over (0: it gives way after one look).  The
+    // default, 20 us, is above the heads' longest A wait in a normal step (stamps, end of the fc2 update -> A ready,
+    // max over heads and steps: 10.0 us in one process, 10.7 / 13.0 us at loopback 2 / 8; step 0 from workgroup
+    // entry: 15.7 us, where the gate may give way early — it only hands over to the full wait).  _HEAD_CHAIN, one
+    // bit per part, default both: 1 the one-wave head's operands in registers from the top of the step (-0.10
+    // us/step alone, -0.09 on top of 2), 2 its logits by wave_sum_tree (-0.60); all three parts: 21.77 -> 20.81
+    const long ga = hopsx_env_int("HOPSX_PERSIST_GATE_A", 1);
+    kn_gate_a = (int)(ga >= 0 && ga <= 2 ? ga : 0);
+    const long gus = hopsx_env_int("HOPSX_PERSIST_GATE_A_US", 20);
+    kn_gate_a_tk = (int)(gus >= 0 && gus <= 1000000 ? gus * 100 : 2000);  // us -> 100 MHz ticks
+    kn_head = (int)(hopsx_env_int("HOPSX_PERSIST_HEAD_CHAIN", 3) & 3);
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1811,7 +1881,9 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.pollw_c = kn_c;
   a.pollw_d = kn_d;
   a.head1w = kn_head1w;
-  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8) | (kn_fill << 16) | (kn_fmax << HAND_FMAX_SHIFT);
+  a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8) | (kn_fill << 16) | (kn_fmax << HAND_FMAX_SHIFT) |
+           (kn_gate_a << HAND_GATEA_SHIFT) | (kn_head & 1 ? HAND_HEAD_REGS : 0) | (kn_head & 2 ? HAND_HEAD_TREE : 0);
+  a.gate_a_tk = kn_gate_a_tk;
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;
   a.inv_gb = 1.f / (float)(world * B);
   if (dp) {
@@ -1896,4 +1968,18 @@ extern "C" void hopsx_mnist_persist_geom(long* g) {
   g[21] = XS_CONV;
   g[22] = TG_WORDS;  // tag granules of hand-off B behind the flag rows (32-bit words)
   g[23] = NFCH;      // chunks of the fc1 slice update (the range of HOPSX_PERSIST_FILL_MAX)
+}
+
+// Probe of common.h wave_sum_tree against wave_sum (tests/test_wave_sum_tree_gpu.py): one wave per row of 64 values,
+// every lane's result of both, out_ref / out_tree [rows][64]
+__global__ __launch_bounds__(64) void wave_sum_probe_k(const float* x, float* out_ref, float* out_tree) {
+  const long e = (long)blockIdx.x * 64 + threadIdx.x;
+  const float v = x[e];
+  out_ref[e] = wave_sum(v);
+  out_tree[e] = wave_sum_tree(v);
+}
+extern "C" int hopsx_wave_sum_probe(const float* x, long rows, float* out_ref, float* out_tree, hipStream_t st) {
+  if (rows < 1 || rows > 65535 || !x || !out_ref || !out_tree) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wave_sum_probe_k, dim3((unsigned)rows), dim3(64), 0, st, x, out_ref, out_tree);
+  return (int)hipGetLastError();
 }
