@@ -423,6 +423,32 @@ HX_PYMOD(HOPSX_MODNAME) {
                         P<float>(dg), P<float>(db), P<float>(ws), M, C, act, P<void>(dres), P<float>(acc),
                         P<float>(zbeta), S(st));
   });
+  m.def("bn_fwd_train_path", [](u x, u y, u res, u acc, int M, int C) {
+    std::vector<int> o(7);
+    hopsx_bn_fwd_train_path(P<void>(x), P<void>(y), P<void>(res), P<float>(acc), M, C, o.data());
+    return o;
+  });
+  m.def("bn_fwd_apply_fin_path", [](u x, u y, u res, u acc, int M, int C) {
+    std::vector<int> o(7);
+    hopsx_bn_fwd_apply_fin_path(P<void>(x), P<void>(y), P<void>(res), P<float>(acc), M, C, o.data());
+    return o;
+  });
+  m.def("bn_fwd_infer_path", [](u x, u y, u res, int M, int C) {
+    std::vector<int> o(7);
+    hopsx_bn_fwd_infer_path(P<void>(x), P<void>(y), P<void>(res), M, C, o.data());
+    return o;
+  });
+  m.def("bn_bwd_path", [](u dy, u x, u y, u dx, u dres, u acc, u zbeta, int M, int C, int act) {
+    std::vector<int> o(7);
+    hopsx_bn_bwd_path(P<void>(dy), P<void>(x), P<void>(y), P<void>(dx), P<void>(dres), P<float>(acc), P<float>(zbeta),
+                      M, C, act, o.data());
+    return o;
+  });
+  m.def("bn_bwd_pre_path", [](u dy, u x, u dx, u acc, int M, int C) {
+    std::vector<int> o(7);
+    hopsx_bn_bwd_pre_path(P<void>(dy), P<void>(x), P<void>(dx), P<float>(acc), M, C, o.data());
+    return o;
+  });
   m.def("embedding_bag_fwd", [](u table, u idx, u offs, int nbags, int dim, long nidx, int bag_len, int mode, u out,
                                 int of32, long ldo, long rows, u st) {
     return hopsx_embedding_bag_fwd(P<float>(table), P<long>(idx), P<long>(offs), nbags, dim, nidx, bag_len, mode,

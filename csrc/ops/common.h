@@ -179,7 +179,10 @@ static inline bool hopsx_disabled(const char* name) {
   const char* env = std::getenv("HOPSX_DISABLE");
   return env && *env && std::strstr(env, name) != nullptr;
 }
-// integer tuning knob from the environment (read on every call: host-side launch sizing only)
+// integer tuning knob from the environment: host-side launch sizing only.  The function itself reads the
+// variable on every call, but most callers keep the result in a function-local static (norm.hip's
+// HOPSX_BN_DEFER_MAXC / _FOLD_MINC / _MAXG / _APPLY_MAXG / _COOP), so such a knob is fixed at its first
+// use in a process: A/B runs and tests set it before the process starts.
 static inline long hopsx_env_int(const char* name, long dflt) {
   const char* e = std::getenv(name);
   return e && *e ? std::atol(e) : dflt;

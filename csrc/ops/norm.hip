@@ -840,13 +840,41 @@ static int ew_grid(long n) {
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Routing.  Every launcher asks ONE decision function for its plan and launches what the plan says;
+// the hopsx_bn_*_path reporters return the same plan without launching (tests assert the route a case
+// names before they compare its numbers).
+enum BnRoute : int {
+  BN_ROUTE_REFUSE = -2,  // the launcher returns -2, nothing launched
+  BN_ROUTE_SCALAR = 0,   // bn_stats_k / bn_finalize_k / bn_apply_k; bn_bwd_reduce_k / bn_bwd_apply_k / bn_grad_acc_k
+  BN_ROUTE_DEFER = 1,    // (bn_colred8_k deferred +) bn_apply_fin8_k / bn_bwd_apply_fin8_k
+  BN_ROUTE_SELFFIN = 2,  // bn_colred8_k finishes itself + bn_apply8_k / bn_bwd_apply8_k
+  BN_ROUTE_FOLD = 3,     // (bn_colred8_k deferred +) bn_fold_k + bn_apply8_k / bn_bwd_apply8_k
+  BN_ROUTE_COOP = 4,     // bn_bwd_coop8_k<R>
+  BN_ROUTE_APPLY = 5     // bn_apply8_k alone (inference)
+};
+struct BnPlan {
+  int route;
+  int R;        // BN_ROUTE_COOP: rows per lane
+  int g;        // reduction grid: colred workgroups (vector), slab gridDim.y (scalar), coop grid
+  int rpb;      // rows per reduction workgroup
+  int ga;       // apply grid
+  int gx;       // scalar: 64-column strips (gridDim.x of the reduction)
+  int reads_y;  // backward: 1 if any kernel of the route loads y
+};
+static constexpr int BN_PLAN_INTS = 7;
+static void bn_plan_out(const BnPlan& p, int* out) {
+  if (!out) return;
+  const int v[BN_PLAN_INTS] = {p.route, p.R, p.g, p.rpb, p.ga, p.gx, p.reads_y};
+  for (int i = 0; i < BN_PLAN_INTS; ++i) out[i] = v[i];
+}
+
 // the one-launch backward (bn_bwd_coop8_k) when a resident grid covers the tensor in one trip
+static size_t bn_coop_shm(int C) { return std::max<size_t>(256 * 16, 3 * (size_t)C) * sizeof(float); }
 template <int R>
-static bool bn_coop_try(const void* dy, const void* x, const void* y, const float* gamma, const float* mean,
-                        const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C, int act,
-                        void* dres, float* acc, hipStream_t st) {
+static long bn_coop_grid(int M, int C) {  // workgroups of bn_bwd_coop8_k<R>, 0 if they are not all resident
   static int n_cu = 0, occ = 0;
-  const size_t shm = std::max<size_t>(256 * 16, 3 * (size_t)C) * sizeof(float);
+  const size_t shm = bn_coop_shm(C);
   if (!n_cu) {
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -860,27 +888,84 @@ static bool bn_coop_try(const void* dy, const void* x, const void* y, const floa
   const int RPI = 256 / (C / 8);
   const long G = ((long)M + (long)RPI * R - 1) / ((long)RPI * R);
   const long cap = (long)n_cu * occ / 2;  // half the resident capacity: see bn_bwd_coop8_k
-  if (G < 1 || G > cap) return false;
-  const BnFin fin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, ws, dgamma, dbeta, 1};
-  const long long spin = 200000000LL;  // 2 s of the 100 MHz wall clock
-  hipLaunchKernelGGL(bn_bwd_coop8_k<R>, dim3((unsigned)G), dim3(256), shm, st, (const bf16_raw*)dy,
-                     (const bf16_raw*)x, (const bf16_raw*)y, gamma, mean, rstd, acc, (bf16_raw*)dx, (bf16_raw*)dres, M,
-                     C, act, fin, spin);
-  return true;
+  return G < 1 || G > cap ? 0 : G;
 }
-
-static bool bn_bwd_coop(const void* dy, const void* x, const void* y, const float* gamma, const float* mean,
-                        const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C, int act,
-                        void* dres, float* acc, hipStream_t st) {
+// rows per lane of the one-launch backward for this shape (grid in G), 0: the two-launch routes
+static int bn_coop_rows(int M, int C, long& G) {
   // off by default: measured SLOWER than the two launches (ResNet-20 111.6k -> 102.7k img/s, ResNet-50
   // B=64 4.15k -> 4.10k; profiles/r2s7_verify2_ab.txt) — fewer workgroups in flight per tensor and the
   // barrier's round trips outweigh the saved launch and re-read.  HOPSX_BN_COOP=1 to A/B.
   static const long on = hopsx_env_int("HOPSX_BN_COOP", 0);
-  if (!on) return false;
-  return bn_coop_try<1>(dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dres, acc, st) ||
-         bn_coop_try<2>(dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dres, acc, st) ||
-         bn_coop_try<4>(dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dres, acc, st) ||
-         bn_coop_try<8>(dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dres, acc, st);
+  if (!on) return 0;
+  if ((G = bn_coop_grid<1>(M, C)) > 0) return 1;
+  if ((G = bn_coop_grid<2>(M, C)) > 0) return 2;
+  if ((G = bn_coop_grid<4>(M, C)) > 0) return 4;
+  if ((G = bn_coop_grid<8>(M, C)) > 0) return 8;
+  return 0;
+}
+template <int R>
+static void bn_coop_launch(long G, const void* dy, const void* x, const void* y, const float* gamma,
+                           const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws,
+                           int M, int C, int act, void* dres, float* acc, hipStream_t st) {
+  const BnFin fin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, ws, dgamma, dbeta, 1};
+  const long long spin = 200000000LL;  // 2 s of the 100 MHz wall clock
+  hipLaunchKernelGGL(bn_bwd_coop8_k<R>, dim3((unsigned)G), dim3(256), bn_coop_shm(C), st, (const bf16_raw*)dy,
+                     (const bf16_raw*)x, (const bf16_raw*)y, gamma, mean, rstd, acc, (bf16_raw*)dx, (bf16_raw*)dres, M,
+                     C, act, fin, spin);
+}
+
+static BnPlan bn_plan_scalar(int M, int C, int act) {
+  BnPlan p{BN_ROUTE_SCALAR, 0, 0, 0, 0, 0, act != ACT_NONE};
+  slab_grid(M, C, p.gx, p.g, p.rpb);
+  p.ga = ew_grid((long)M * C);
+  return p;
+}
+static BnPlan bn_plan_fwd_train(const void* x, const void* y, const void* residual, const float* acc, int M, int C) {
+  if (!(acc && bn_vec_ok(C, {x, y, residual}))) return bn_plan_scalar(M, C, 0);
+  BnPlan p{bn_defer(C) ? BN_ROUTE_DEFER : BN_ROUTE_SELFFIN, 0, 0, 0, 0, 0, 0};
+  p.g = colred_grid(M, C, p.rpb);
+  p.ga = apply_grid((long)M * C / 8, C);
+  return p;
+}
+static BnPlan bn_plan_fwd_apply_fin(const void* x, const void* y, const void* residual, const float* acc, int M,
+                                    int C) {
+  BnPlan p{BN_ROUTE_REFUSE, 0, 0, 0, 0, 0, 0};
+  if (!acc || !bn_vec_ok(C, {x, y, residual})) return p;
+  p.route = bn_fold_first(C) ? BN_ROUTE_FOLD : BN_ROUTE_DEFER;
+  p.ga = apply_grid((long)M * C / 8, C);
+  return p;
+}
+static BnPlan bn_plan_fwd_infer(const void* x, const void* y, const void* residual, int M, int C) {
+  if (!bn_vec_ok(C, {x, y, residual})) return bn_plan_scalar(M, C, 0);
+  BnPlan p{BN_ROUTE_APPLY, 0, 0, 0, 0, 0, 0};
+  p.ga = apply_grid((long)M * C / 8, C);
+  return p;
+}
+static BnPlan bn_plan_bwd_pre(const void* dy, const void* x, const void* dx, const float* acc, int M, int C) {
+  BnPlan p{BN_ROUTE_REFUSE, 0, 0, 0, 0, 0, 0};
+  if (!acc || !bn_vec_ok(C, {dy, x, dx})) return p;
+  p.route = bn_fold_first(C) ? BN_ROUTE_FOLD : BN_ROUTE_DEFER;
+  p.ga = apply_grid((long)M * C / 8, C);
+  return p;
+}
+// zbeta: as the launcher received it (HOPSX_DISABLE=bn_zmask is applied here)
+static BnPlan bn_plan_bwd(const void* dy, const void* x, const void* y, const void* dx, const void* dresidual,
+                          const float* acc, const float* zbeta, int M, int C, int act) {
+  if (!(acc && bn_vec_ok(C, {dy, x, y, dx, dresidual}))) return bn_plan_scalar(M, C, act);
+  BnPlan p{BN_ROUTE_SELFFIN, 0, 0, 0, 0, 0, act != ACT_NONE};
+  long G = 0;
+  if ((p.R = bn_coop_rows(M, C, G)) > 0) {
+    p.route = BN_ROUTE_COOP;
+    p.g = (int)G;
+    p.rpb = 256 / (C / 8) * p.R;
+    return p;
+  }
+  p.g = colred_grid(M, C, p.rpb);
+  p.ga = apply_grid((long)M * C / 8, C);
+  if (bn_defer(C)) p.route = bn_fold_first(C) ? BN_ROUTE_FOLD : BN_ROUTE_DEFER;
+  // only the deferred pair takes act' from z in BOTH kernels (the plain apply has no zmask)
+  if (p.route == BN_ROUTE_DEFER && zbeta && !hopsx_disabled("bn_zmask") && act == ACT_RELU) p.reads_y = 0;
+  return p;
 }
 
 // timeout flag of the coop barrier (tests)
@@ -896,31 +981,35 @@ extern "C" int hopsx_bn_fwd_train(const void* x, void* y, const float* gamma, co
                                   float eps, int M, int C, const void* residual, int act, float* acc,
                                   hipStream_t st) {
   const long n = (long)M * C;
-  if (acc && bn_vec_ok(C, {x, y, residual})) {  // acc: BN_NREP x 2C floats + arrival words, zero at rest
-    int rpb;
-    const int g = colred_grid(M, C, rpb);
-    const int defer = bn_defer(C);
+  const BnPlan p = bn_plan_fwd_train(x, y, residual, acc, M, C);
+  if (p.route != BN_ROUTE_SCALAR) {  // acc: BN_NREP x 2C floats + arrival words, zero at rest
+    const int defer = p.route == BN_ROUTE_DEFER;
     const BnFin fin{mean_out, rstd_out, running_mean, running_var, momentum, eps, nullptr, nullptr, nullptr, defer};
-    hipLaunchKernelGGL(bn_colred8_k<0>, dim3(g), dim3(256), 0, st, (const bf16_raw*)x, nullptr, nullptr, nullptr,
-                       nullptr, acc, M, C, rpb, 0, fin);
+    hipLaunchKernelGGL(bn_colred8_k<0>, dim3(p.g), dim3(256), 0, st, (const bf16_raw*)x, nullptr, nullptr, nullptr,
+                       nullptr, acc, M, C, p.rpb, 0, fin);
     if (defer)  // the apply folds the replicas (the same launch the conv-epilogue statistics use)
-      hipLaunchKernelGGL(bn_apply_fin8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)x,
-                         (bf16_raw*)y, gamma, beta, acc, n / 8, M, C, (const bf16_raw*)residual, act, fin);
+      hipLaunchKernelGGL(bn_apply_fin8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
+                         acc, n / 8, M, C, (const bf16_raw*)residual, act, fin);
     else
-      hipLaunchKernelGGL(bn_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y,
-                         gamma, beta, mean_out, rstd_out, 0, eps, n / 8, C, (const bf16_raw*)residual, act);
+      hipLaunchKernelGGL(bn_apply8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
+                         mean_out, rstd_out, 0, eps, n / 8, C, (const bf16_raw*)residual, act);
     return (int)hipGetLastError();
   }
   hopsx_zero(mean_out, C * sizeof(float), st);
   hopsx_zero(rstd_out, C * sizeof(float), st);
-  int gx, gy, rpb;
-  slab_grid(M, C, gx, gy, rpb);
-  hipLaunchKernelGGL(bn_stats_k, dim3(gx, gy), dim3(256), 0, st, (const bf16_raw*)x, mean_out, rstd_out, M, C, rpb);
+  hipLaunchKernelGGL(bn_stats_k, dim3(p.gx, p.g), dim3(256), 0, st, (const bf16_raw*)x, mean_out, rstd_out, M, C,
+                     p.rpb);
   hipLaunchKernelGGL(bn_finalize_k, dim3((C + 255) / 256), dim3(256), 0, st, mean_out, rstd_out, running_mean,
                      running_var, momentum, eps, M, C);
-  hipLaunchKernelGGL(bn_apply_k, dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
-                     mean_out, rstd_out, 0, eps, n, C, (const bf16_raw*)residual, act);
+  hipLaunchKernelGGL(bn_apply_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta, mean_out,
+                     rstd_out, 0, eps, n, C, (const bf16_raw*)residual, act);
   return (int)hipGetLastError();
+}
+extern "C" int hopsx_bn_fwd_train_path(const void* x, const void* y, const void* residual, const float* acc, int M,
+                                       int C, int* out) {
+  const BnPlan p = bn_plan_fwd_train(x, y, residual, acc, M, C);
+  bn_plan_out(p, out);
+  return p.route;
 }
 
 // Training forward whose statistics are already in `acc` (accumulated by the producing conv's
@@ -930,18 +1019,25 @@ extern "C" int hopsx_bn_fwd_apply_fin(const void* x, void* y, const float* gamma
                                       float* rstd_out, float* running_mean, float* running_var, float momentum,
                                       float eps, int M, int C, const void* residual, int act, float* acc,
                                       hipStream_t st) {
-  if (!acc || !bn_vec_ok(C, {x, y, residual})) return -2;
+  const BnPlan p = bn_plan_fwd_apply_fin(x, y, residual, acc, M, C);
+  if (p.route == BN_ROUTE_REFUSE) return -2;
   const long n = (long)M * C;
   const BnFin fin{mean_out, rstd_out, running_mean, running_var, momentum, eps, nullptr, nullptr, nullptr};
-  if (bn_fold_first(C)) {
+  if (p.route == BN_ROUTE_FOLD) {
     hipLaunchKernelGGL(bn_fold_k<0>, dim3((C + 255) / 256), dim3(256), 0, st, acc, M, C, fin);
-    hipLaunchKernelGGL(bn_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y,
-                       gamma, beta, mean_out, rstd_out, 0, eps, n / 8, C, (const bf16_raw*)residual, act);
+    hipLaunchKernelGGL(bn_apply8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
+                       mean_out, rstd_out, 0, eps, n / 8, C, (const bf16_raw*)residual, act);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(bn_apply_fin8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)x,
-                     (bf16_raw*)y, gamma, beta, acc, n / 8, M, C, (const bf16_raw*)residual, act, fin);
+  hipLaunchKernelGGL(bn_apply_fin8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta, acc,
+                     n / 8, M, C, (const bf16_raw*)residual, act, fin);
   return (int)hipGetLastError();
+}
+extern "C" int hopsx_bn_fwd_apply_fin_path(const void* x, const void* y, const void* residual, const float* acc, int M,
+                                           int C, int* out) {
+  const BnPlan p = bn_plan_fwd_apply_fin(x, y, residual, acc, M, C);
+  bn_plan_out(p, out);
+  return p.route;
 }
 
 extern "C" int hopsx_bn_prestats_ok(int C) { return bn_vec_ok(C, {}) ? 1 : 0; }
@@ -950,14 +1046,20 @@ extern "C" int hopsx_bn_fwd_infer(const void* x, void* y, const float* gamma, co
                                   const float* running_mean, const float* running_var, float eps, int M, int C,
                                   const void* residual, int act, hipStream_t st) {
   const long n = (long)M * C;
-  if (bn_vec_ok(C, {x, y, residual})) {
-    hipLaunchKernelGGL(bn_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y,
-                       gamma, beta, running_mean, running_var, 1, eps, n / 8, C, (const bf16_raw*)residual, act);
+  const BnPlan p = bn_plan_fwd_infer(x, y, residual, M, C);
+  if (p.route == BN_ROUTE_APPLY) {
+    hipLaunchKernelGGL(bn_apply8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
+                       running_mean, running_var, 1, eps, n / 8, C, (const bf16_raw*)residual, act);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(bn_apply_k, dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
+  hipLaunchKernelGGL(bn_apply_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)x, (bf16_raw*)y, gamma, beta,
                      running_mean, running_var, 1, eps, n, C, (const bf16_raw*)residual, act);
   return (int)hipGetLastError();
+}
+extern "C" int hopsx_bn_fwd_infer_path(const void* x, const void* y, const void* residual, int M, int C, int* out) {
+  const BnPlan p = bn_plan_fwd_infer(x, y, residual, M, C);
+  bn_plan_out(p, out);
+  return p.route;
 }
 
 // The column sums already sit in acc's replica rows (a consumer conv's dgrad epilogue reduced them:
@@ -966,62 +1068,70 @@ extern "C" int hopsx_bn_fwd_infer(const void* x, void* y, const float* gamma, co
 extern "C" int hopsx_bn_bwd_pre(const void* dy, const void* x, const float* gamma, const float* mean,
                                 const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C,
                                 float* acc, hipStream_t st) {
-  if (!acc || !bn_vec_ok(C, {dy, x, dx})) return -2;
+  const BnPlan p = bn_plan_bwd_pre(dy, x, dx, acc, M, C);
+  if (p.route == BN_ROUTE_REFUSE) return -2;
   const long n = (long)M * C;
   const BnFin fin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, ws, dgamma, dbeta, 1};
-  if (bn_fold_first(C)) {
+  if (p.route == BN_ROUTE_FOLD) {
     hipLaunchKernelGGL(bn_fold_k<1>, dim3((C + 255) / 256), dim3(256), 0, st, acc, M, C, fin);
-    hipLaunchKernelGGL(bn_bwd_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)dy,
-                       (const bf16_raw*)x, (const bf16_raw*)nullptr, gamma, mean, rstd, ws, (bf16_raw*)dx,
-                       (bf16_raw*)nullptr, n / 8, M, C, (int)ACT_NONE);
+    hipLaunchKernelGGL(bn_bwd_apply8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                       (const bf16_raw*)nullptr, gamma, mean, rstd, ws, (bf16_raw*)dx, (bf16_raw*)nullptr, n / 8, M, C,
+                       (int)ACT_NONE);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(bn_bwd_apply_fin8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)dy,
-                     (const bf16_raw*)x, (const bf16_raw*)nullptr, gamma, mean, rstd, acc, (bf16_raw*)dx,
-                     (bf16_raw*)nullptr, n / 8, M, C, (int)ACT_NONE, fin, (const float*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_apply_fin8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                     (const bf16_raw*)nullptr, gamma, mean, rstd, acc, (bf16_raw*)dx, (bf16_raw*)nullptr, n / 8, M, C,
+                     (int)ACT_NONE, fin, (const float*)nullptr);
   return (int)hipGetLastError();
+}
+extern "C" int hopsx_bn_bwd_pre_path(const void* dy, const void* x, const void* dx, const float* acc, int M, int C,
+                                     int* out) {
+  const BnPlan p = bn_plan_bwd_pre(dy, x, dx, acc, M, C);
+  bn_plan_out(p, out);
+  return p.route;
 }
 
 // zbeta: the BN's beta when its forward had no residual (ReLU: act' taken from x, see bn_shift); else null
 extern "C" int hopsx_bn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* mean,
                             const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C,
                             int act, void* dresidual, float* acc, const float* zbeta, hipStream_t st) {
+  const BnPlan p = bn_plan_bwd(dy, x, y, dx, dresidual, acc, zbeta, M, C, act);
   if (hopsx_disabled("bn_zmask")) zbeta = nullptr;
   const long n = (long)M * C;
-  if (acc && bn_vec_ok(C, {dy, x, y, dx, dresidual})) {  // acc: BN_NREP x 2C floats + arrival words, zero at rest
-    int rpb;
-    const int g = colred_grid(M, C, rpb);
-    if (bn_bwd_coop(dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dresidual, acc, st))
-      return (int)hipGetLastError();
-    const int defer = bn_defer(C);
+  if (p.route == BN_ROUTE_COOP) {
+    const auto launch = p.R == 1 ? bn_coop_launch<1> : p.R == 2 ? bn_coop_launch<2> : p.R == 4 ? bn_coop_launch<4>
+                                                                                                : bn_coop_launch<8>;
+    launch(p.g, dy, x, y, gamma, mean, rstd, dx, dgamma, dbeta, ws, M, C, act, dresidual, acc, st);
+    return (int)hipGetLastError();
+  }
+  if (p.route != BN_ROUTE_SCALAR) {  // acc: BN_NREP x 2C floats + arrival words, zero at rest
+    const int defer = p.route != BN_ROUTE_SELFFIN;
     const BnFin fin{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, ws, dgamma, dbeta, defer};
-    hipLaunchKernelGGL(bn_colred8_k<1>, dim3(g), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
-                       (const bf16_raw*)y, mean, rstd, acc, M, C, rpb, act, fin, gamma, zbeta);
-    if (defer && bn_fold_first(C)) {  // (wide channels: y is read, the plain apply has no zmask)
+    hipLaunchKernelGGL(bn_colred8_k<1>, dim3(p.g), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                       (const bf16_raw*)y, mean, rstd, acc, M, C, p.rpb, act, fin, gamma, zbeta);
+    if (p.route == BN_ROUTE_FOLD)  // (wide channels: y is read, the plain apply has no zmask)
       hipLaunchKernelGGL(bn_fold_k<1>, dim3((C + 255) / 256), dim3(256), 0, st, acc, M, C, fin);
-      hipLaunchKernelGGL(bn_bwd_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)dy,
-                         (const bf16_raw*)x, (const bf16_raw*)y, gamma, mean, rstd, ws, (bf16_raw*)dx,
-                         (bf16_raw*)dresidual, n / 8, M, C, act);
-      return (int)hipGetLastError();
-    }
-    if (defer) {
-      hipLaunchKernelGGL(bn_bwd_apply_fin8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)dy,
-                         (const bf16_raw*)x, (const bf16_raw*)y, gamma, mean, rstd, acc, (bf16_raw*)dx,
-                         (bf16_raw*)dresidual, n / 8, M, C, act, fin, zbeta);
-      return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(bn_bwd_apply8_k, dim3(apply_grid(n / 8, C)), dim3(256), 0, st, (const bf16_raw*)dy,
-                       (const bf16_raw*)x, (const bf16_raw*)y, gamma, mean, rstd, ws, (bf16_raw*)dx,
-                       (bf16_raw*)dresidual, n / 8, M, C, act);
+    if (p.route == BN_ROUTE_DEFER)
+      hipLaunchKernelGGL(bn_bwd_apply_fin8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                         (const bf16_raw*)y, gamma, mean, rstd, acc, (bf16_raw*)dx, (bf16_raw*)dresidual, n / 8, M, C,
+                         act, fin, zbeta);
+    else
+      hipLaunchKernelGGL(bn_bwd_apply8_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                         (const bf16_raw*)y, gamma, mean, rstd, ws, (bf16_raw*)dx, (bf16_raw*)dresidual, n / 8, M, C,
+                         act);
     return (int)hipGetLastError();
   }
   hopsx_zero(ws, 2 * C * sizeof(float), st);
-  int gx, gy, rpb;
-  slab_grid(M, C, gx, gy, rpb);
-  hipLaunchKernelGGL(bn_bwd_reduce_k, dim3(gx, gy), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
-                     (const bf16_raw*)y, mean, rstd, ws, M, C, rpb, act);
-  hipLaunchKernelGGL(bn_bwd_apply_k, dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+  hipLaunchKernelGGL(bn_bwd_reduce_k, dim3(p.gx, p.g), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
+                     (const bf16_raw*)y, mean, rstd, ws, M, C, p.rpb, act);
+  hipLaunchKernelGGL(bn_bwd_apply_k, dim3(p.ga), dim3(256), 0, st, (const bf16_raw*)dy, (const bf16_raw*)x,
                      (const bf16_raw*)y, gamma, mean, rstd, ws, (bf16_raw*)dx, (bf16_raw*)dresidual, n, M, C, act);
   hipLaunchKernelGGL(bn_grad_acc_k, dim3((C + 255) / 256), dim3(256), 0, st, ws, dgamma, dbeta, C);
   return (int)hipGetLastError();
+}
+extern "C" int hopsx_bn_bwd_path(const void* dy, const void* x, const void* y, const void* dx, const void* dresidual,
+                                 const float* acc, const float* zbeta, int M, int C, int act, int* out) {
+  const BnPlan p = bn_plan_bwd(dy, x, y, dx, dresidual, acc, zbeta, M, C, act);
+  bn_plan_out(p, out);
+  return p.route;
 }

@@ -116,6 +116,20 @@ int hopsx_bn_fwd_infer(const void* x, void* y, const float* gamma, const float* 
 int hopsx_bn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* mean,
                  const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C, int act,
                  void* dresidual, float* acc, const float* zbeta, hipStream_t st);
+// The kernel sequence a BN launcher runs for exactly these routing arguments, nothing launched (launcher
+// and reporter share one decision function, norm.hip bn_plan_*).  Return value = out[0]: 0 scalar kernels,
+// 1 vector with the deferred fold (*_fin8_k), 2 vector with the self-finishing bn_colred8_k + plain apply,
+// 3 fold-first (bn_fold_k + plain apply), 4 one-launch cooperative backward, 5 bn_apply8_k alone (inference),
+// -2 refused.  out[7] (may be null) = {route, R rows per lane of the cooperative kernel, reduction grid
+// (scalar: gridDim.y), rows per reduction workgroup, apply grid, scalar gridDim.x, backward reads y}.
+int hopsx_bn_fwd_train_path(const void* x, const void* y, const void* residual, const float* acc, int M, int C,
+                            int* out);
+int hopsx_bn_fwd_apply_fin_path(const void* x, const void* y, const void* residual, const float* acc, int M, int C,
+                                int* out);
+int hopsx_bn_fwd_infer_path(const void* x, const void* y, const void* residual, int M, int C, int* out);
+int hopsx_bn_bwd_path(const void* dy, const void* x, const void* y, const void* dx, const void* dresidual,
+                      const float* acc, const float* zbeta, int M, int C, int act, int* out);
+int hopsx_bn_bwd_pre_path(const void* dy, const void* x, const void* dx, const float* acc, int M, int C, int* out);
 
 // ---- direct MFMA convs for short reductions (conv_mfma.hip) ----
 // ---- whole wide&deep training step in one workgroup (widedeep_step.hip) ----

@@ -1416,6 +1416,66 @@ def gap_bwd_reference(dy, x_shape, dtype=torch.float64):
     return (dy.to(dtype) / (H * W)).view(B, 1, 1, C).expand(B, H, W, C).contiguous()
 
 
+def _act_name(act):
+    return {0: None, "none": None, 1: "relu", 2: "sigmoid", 3: "tanh"}.get(act, act)
+
+
+def bn_stats_reference(x, dtype=torch.float64):
+    """Plain-tensor statement of norm.hip's statistics pass for ``x`` [M, C] on the host: returns
+    ``(sum, sumsq, mean, var_biased, var_unbiased)`` per channel in ``dtype``; the variance is the kernels'
+    ``max(sumsq / M - mean^2, 0)`` and the unbiased one its ``M / (M - 1)`` multiple (M = 1: the biased one)."""
+    xd = x.to(dtype)
+    M = xd.shape[0]
+    s, q = xd.sum(0), (xd * xd).sum(0)
+    mean = s / M
+    var = (q / M - mean * mean).clamp_min(0)
+    return s, q, mean, var, (var * M / (M - 1) if M > 1 else var)
+
+
+def bn_reference(x, gamma, beta, mean, rstd_or_var, eps=1e-5, residual=None, act=None, var_mode=False,
+                 dtype=torch.float64):
+    """The unrounded ``act((x - mean) * rs * gamma + beta + residual)`` of norm.hip's apply kernels for ``x`` [M, C];
+    ``rs`` is ``rstd_or_var`` itself, or ``1 / sqrt(rstd_or_var + eps)`` with ``var_mode`` (inference from the
+    running variance).  ``gamma`` / ``beta`` / ``residual`` None: 1 / 0 / 0."""
+    d = lambda t: t.to(dtype)  # noqa: E731
+    rs = d(rstd_or_var)
+    if var_mode:
+        rs = 1.0 / torch.sqrt(rs + torch.tensor(eps, dtype=torch.float32).to(dtype))
+    v = (d(x) - d(mean)) * rs
+    if gamma is not None:
+        v = v * d(gamma)
+    if beta is not None:
+        v = v + d(beta)
+    if residual is not None:
+        v = v + d(residual)
+    name = _act_name(act)
+    return v if name is None else {"relu": torch.relu, "sigmoid": torch.sigmoid, "tanh": torch.tanh}[name](v)
+
+
+def bn_bwd_reference(dy, x, y, gamma, beta, mean, rstd, act=None, dtype=torch.float64):
+    """norm.hip's backward for ``dy`` / ``x`` [M, C]: returns ``(dz, sum_dz, sum_dz_xhat, dx)``, all unrounded, with
+    ``dz = dy * act'``, ``xhat = (x - mean) * rstd`` and
+    ``dx = gamma * rstd * (dz - sum_dz / M - xhat * sum_dz_xhat / M)``.  ``act'`` is expressed through the stored
+    output ``y`` (common.h act_grad_from_out: ``y > 0`` / ``y (1 - y)`` / ``1 - y^2``); with ``y`` None it comes from
+    the reference's own ``z = xhat * gamma + beta`` (no residual): the sign of z for relu, the exact derivative
+    otherwise."""
+    d = lambda t: t.to(dtype)  # noqa: E731
+    M = x.shape[0]
+    xhat = (d(x) - d(mean)) * d(rstd)
+    name = _act_name(act)
+    dz = d(dy)
+    if name is not None:
+        if y is None:
+            yy = bn_reference(x, gamma, beta, mean, rstd, act=name, dtype=dtype)
+        else:
+            yy = d(y)
+        dz = dz * {"relu": lambda v: (v > 0).to(dtype), "sigmoid": lambda v: v * (1 - v),
+                   "tanh": lambda v: 1 - v * v}[name](yy)
+    s1, s2 = dz.sum(0), (dz * xhat).sum(0)
+    k1 = d(rstd) if gamma is None else d(gamma) * d(rstd)
+    return dz, s1, s2, k1 * (dz - s1 / M - xhat * s2 / M)
+
+
 def dropout_keep_reference(rng, salt: int, shape, p: float):
     """The keep mask of a Dropout over a tensor of ``shape``, stated on the host: runtime.persist.dropout_keep at
     the LINEAR index of every element (for the Dropout fused into the max-pool: the NHWC index of the pooled

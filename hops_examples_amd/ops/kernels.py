@@ -818,6 +818,44 @@ def bn_bwd_pre(g, x, gamma, mean, rstd, dgamma, dbeta, ws, acc, out=None):
     return out
 
 
+BN_ROUTES = {0: "scalar", 1: "defer", 2: "selffin", 3: "fold", 4: "coop", 5: "apply", -2: "refuse"}
+
+
+def _bn_plan(v) -> dict:
+    """A launcher's plan (csrc/ops/norm.hip BnPlan): ``route`` one of BN_ROUTES' names, ``R`` the cooperative
+    kernel's rows per lane, ``g`` / ``rpb`` the reduction grid (scalar: gridDim.y) and its rows per workgroup,
+    ``ga`` the apply grid, ``gx`` the scalar reduction's column strips, ``reads_y`` whether the backward loads y."""
+    return dict(route=BN_ROUTES[v[0]], code=v[0], R=v[1], g=v[2], rpb=v[3], ga=v[4], gx=v[5], reads_y=bool(v[6]))
+
+
+def bn_fwd_train_path(x2d, out, residual=None) -> dict:
+    """The kernels bn_fwd_train runs for these arguments; nothing is launched (hopsx_bn_fwd_train_path)."""
+    M, C = x2d.shape
+    return _bn_plan(_C.ext().bn_fwd_train_path(ptr(x2d), ptr(out), ptr(residual), ptr(bn_acc(x2d.device, C)), M, C))
+
+
+def bn_fwd_apply_fin_path(x2d, out, residual=None, alt=False) -> dict:
+    M, C = x2d.shape
+    return _bn_plan(_C.ext().bn_fwd_apply_fin_path(ptr(x2d), ptr(out), ptr(residual),
+                                                   ptr(bn_acc(x2d.device, C, alt=alt)), M, C))
+
+
+def bn_fwd_infer_path(x2d, out, residual=None) -> dict:
+    M, C = x2d.shape
+    return _bn_plan(_C.ext().bn_fwd_infer_path(ptr(x2d), ptr(out), ptr(residual), M, C))
+
+
+def bn_bwd_path(dy, x, y, out, act=0, dresidual=None, zbeta=None) -> dict:
+    M, C = x.shape
+    return _bn_plan(_C.ext().bn_bwd_path(ptr(dy), ptr(x), ptr(y), ptr(out), ptr(dresidual), ptr(bn_acc(dy.device, C)),
+                                         ptr(zbeta), M, C, act_id(act)))
+
+
+def bn_bwd_pre_path(g, x, out, acc) -> dict:
+    M, C = x.shape
+    return _bn_plan(_C.ext().bn_bwd_pre_path(ptr(g), ptr(x), ptr(out), ptr(acc), M, C))
+
+
 # ------------------------------------------------------------ embedding bag
 def embedding_bag_fwd(table, idx, offsets, mode, out, ldo=None, bag_len=1):
     """Bags are given by ``offsets`` or, without offsets, by a fixed ``bag_len`` (idx [bags, bag_len])."""
