@@ -48,7 +48,7 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 // The declarations, set_deterministic, det_lost and dbg_read below are generated from it.
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
-#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval)
+#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval) X(topk)
 #define X(tag)                              \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
@@ -265,6 +265,12 @@ HX_PYMOD(HOPSX_MODNAME) {
   m.def("zero", [](u p, long bytes, u st) { return hopsx_zero(P<void>(p), bytes, S(st)); });
   m.def("nonfinite", [](u x, long n, int is_bf16, u out, u st) {
     return hopsx_nonfinite(P<void>(x), n, is_bf16, P<unsigned>(out), S(st));
+  });
+  m.def("softmax_topk", [](u x, int is_bf16, int B, int C, int k, u ids, u scores, int max_wg, u st) {
+    return hopsx_softmax_topk(P<void>(x), is_bf16, B, C, k, P<int>(ids), P<float>(scores), max_wg, S(st));
+  });
+  m.def("softmax_topk_path", [](u x, int is_bf16, int B, int C, int k, u ids, u scores) {
+    return hopsx_softmax_topk_path(P<void>(x), is_bf16, B, C, k, P<int>(ids), P<float>(scores));
   });
   m.def("linear_bwd_pair", [](u dy, u w, u x, u dx, u yprev, int act_prev, u colsum, u ay, int aact, u dw, u db,
                               int M, int N, int K, std::vector<int> pool, u pam, u px, u prng, unsigned psalt,

@@ -247,6 +247,15 @@ int hopsx_zero(void* p, long bytes, hipStream_t st);
 // NaN / Inf counts of an fp32 or bf16 tensor: out[0] += #NaN, out[1] += #Inf (elementwise.hip)
 int hopsx_nonfinite(const void* x, long n, int is_bf16, unsigned* out, hipStream_t st);
 
+// ---- row softmax + top-k of logits [B][C], fp32 or bf16 (topk.hip) ----
+// ids int32 [B][k]: the k largest logits' classes, largest first, lower class first among equals; scores fp32
+// [B][k]: their softmax probabilities.  1 <= k <= 8, k <= C.  max_workgroups: 0 = default grid cap.  One kernel
+// launch, nothing else (graph-safe).  hipErrorInvalidValue, nothing launched: what _path refuses.
+int hopsx_softmax_topk(const void* x, int is_bf16, int B, int C, int k, int* ids, float* scores, int max_workgroups,
+                       hipStream_t st);
+// the launcher's route: 0 wave per row, 1 workgroup per row, -2 refused
+int hopsx_softmax_topk_path(const void* x, int is_bf16, int B, int C, int k, const int* ids, const float* scores);
+
 // ---- embedding bag (embedding.hip) ----
 int hopsx_embedding_bag_fwd(const float* table, const long* idx, const long* offsets, int nbags, int dim,
                             long nidx, int bag_len, int mode, void* out, int out_f32, long ldo, long rows,

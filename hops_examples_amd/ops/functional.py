@@ -1416,6 +1416,24 @@ def gap_bwd_reference(dy, x_shape, dtype=torch.float64):
     return (dy.to(dtype) / (H * W)).view(B, 1, 1, C).expand(B, H, W, C).contiguous()
 
 
+def softmax_topk_reference(logits, k: int, dtype=torch.float64):
+    """Plain-tensor statement of topk.hip on the host: ``(ids int32 [B, k], scores [B, k] in dtype)`` of logits
+    [B, C].  The ids are the k largest logits per row, largest first, the lower class first among equal values: a
+    stable sort of the negated values (numpy ``lexsort`` on (index, -value) is the same order), taken on the logits
+    themselves, so no rounding takes part and bf16 inputs widen exactly.  The scores are those entries of a ``dtype``
+    softmax.  ``dtype=torch.float32`` is the fp32 yardstick of the kernel's arithmetic: its distance to the fp64
+    scores measures what an fp32 softmax of the same logits can do (as ``persist_eval.reference_logits``)."""
+    import numpy as np
+
+    z = logits.detach().cpu()
+    if z.dim() != 2 or not 1 <= int(k) <= z.shape[1]:
+        raise ValueError(f"softmax_topk_reference: logits [B, C] and 1 <= k <= C expected, got {tuple(z.shape)}, k={k}")
+    order = np.argsort(-z.to(torch.float64).numpy(), axis=1, kind="stable")[:, :int(k)]
+    ids = torch.from_numpy(np.ascontiguousarray(order))
+    scores = torch.softmax(z.to(dtype), dim=-1).gather(1, ids)
+    return ids.to(torch.int32), scores
+
+
 def _act_name(act):
     return {0: None, "none": None, 1: "relu", 2: "sigmoid", 3: "tanh"}.get(act, act)
 

@@ -969,6 +969,61 @@ def nonfinite_counts(x, out=None):
     return out
 
 
+# ------------------------------------------------------------ softmax + top-k
+TOPK_MAX = 8
+
+
+def _topk_args(logits, k, ids, scores, what):
+    """Validated (B, C, k) of a softmax_topk call: every refusal is raised here, before any launch or allocation."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{what}: logits [B, C] expected")
+    if logits.dtype not in (F32, BF16):
+        raise ValueError(f"{what}: fp32 or bf16 logits expected, got {logits.dtype}")
+    if not logits.is_cuda:
+        raise ValueError(f"{what}: expected a GPU tensor")
+    if not logits.is_contiguous():
+        raise ValueError(f"{what}: expected contiguous logits")
+    B, C = logits.shape
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX or k > C:
+        raise ValueError(f"{what}: 1 <= k <= min({TOPK_MAX}, C = {C}) expected, got k = {k}")
+    if B > 0x7FFFFFFF or C > 0x7FFFFFFF:
+        raise ValueError(f"{what}: B and C must fit in int32")
+    for t, dt, name in ((ids, torch.int32, "ids"), (scores, F32, "scores")):
+        if t is None:
+            continue
+        if t.dtype != dt or not t.is_cuda or t.device != logits.device or not t.is_contiguous() \
+                or tuple(t.shape) != (B, k):
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} [{B}, {k}] tensor on {logits.device}")
+    return B, C, k
+
+
+def softmax_topk(logits, k, ids=None, scores=None, max_workgroups=0):
+    """(ids int32 [B, k], scores fp32 [B, k]) of fp32 / bf16 logits [B, C]: the k largest logits' classes per row,
+    largest first and the lower class first among equals, with their softmax probabilities (csrc/ops/topk.hip).
+    1 <= k <= 8, k <= C.  One kernel launch: capturable.  ``max_workgroups`` caps the grid (0: default)."""
+    B, C, k = _topk_args(logits, k, ids, scores, "softmax_topk")
+    if int(max_workgroups) < 0:
+        raise ValueError("softmax_topk: max_workgroups >= 0 expected")
+    if ids is None:
+        ids = torch.empty(B, k, device=logits.device, dtype=torch.int32)
+    if scores is None:
+        scores = torch.empty(B, k, device=logits.device, dtype=F32)
+    if B:
+        check(_C.ext().softmax_topk(ptr(logits), int(logits.dtype == BF16), B, C, k, ptr(ids), ptr(scores),
+                                    int(max_workgroups), stream()), "softmax_topk")
+    return ids, scores
+
+
+def softmax_topk_path(logits, k) -> int:
+    """The kernel softmax_topk runs for these arguments: 0 a wave per row, 1 a workgroup per row, -2 refused (the
+    launcher's own decision, csrc/ops/topk.hip hopsx_softmax_topk_path)."""
+    B, C, k = _topk_args(logits, k, None, None, "softmax_topk_path")
+    # the route depends on C alone: the outputs (and the logits of an empty batch, which have no storage) are stood
+    # in for by a non-null 16-byte-aligned address that the query only inspects, so nothing is allocated
+    return _C.ext().softmax_topk_path(ptr(logits) if B else 16, int(logits.dtype == BF16), B, C, k, 16, 16)
+
+
 # --------------------------------------------------------- fused classifier head
 _MLP_WS: dict = {}
 
