@@ -117,7 +117,8 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_conv2d_fwd_res(P<void>(x), P<void>(w), g.data(), P<void>(out), P<float>(bias), act,
                                 P<void>(residual), S(st));
   });
-  m.def("conv2d_fwd_res_path", [](std::vector<int> g) { return hopsx_conv2d_fwd_res_path(g.data()); });
+  m.def("conv2d_fwd_path", [](std::vector<int> g, int kind) { return hopsx_conv2d_fwd_path(g.data(), kind); });
+  m.def("conv2d_dgrad_path", [](std::vector<int> g, int flags) { return hopsx_conv2d_dgrad_path(g.data(), flags); });
   m.def("conv2d_dgrad", [](u dy, u w, std::vector<int> g, u dx, u yprev, int act, u colsum, u y, int yact, u addend,
                            u st) {
     return hopsx_conv2d_dgrad(P<void>(dy), P<void>(w), g.data(), P<void>(dx), P<void>(yprev), act, P<float>(colsum),

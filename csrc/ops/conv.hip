@@ -4,6 +4,9 @@
 //   wgrad : dW[co][k=(kh,kw,ci)]   += dY^T[co][m] . im2col(X)[m][k]     (split-K, fp32 atomics)
 // The gathers run inside the LDS staging of gemm_core.h, so no im2col buffer
 // ever touches HBM.
+#include <algorithm>
+#include <type_traits>
+
 #include "gemm_core.h"
 #include "gemm_glds.h"
 #include "ops_api.h"
@@ -11,15 +14,6 @@
 HOPSX_DET_TU(conv)
 
 using namespace hopsx;
-
-static ConvGeom make_geom(const int* g) {
-  ConvGeom c;
-  c.B = g[0]; c.H = g[1]; c.W = g[2]; c.C = g[3];
-  c.OH = g[4]; c.OW = g[5]; c.CO = g[6];
-  c.KH = g[7]; c.KW = g[8]; c.sh = g[9]; c.sw = g[10]; c.ph = g[11]; c.pw = g[12]; c.dh = g[13]; c.dw = g[14];
-  c.init_div();
-  return c;
-}
 
 // ---------------------------------------------------------------------------
 // Direct conv for tiny reductions (K = KH*KW*Cin <= 64: the Cin=1 input layers
@@ -465,7 +459,8 @@ constexpr int kConvTk = 16384;      // tile tickets per role
 __device__ float g_conv_ws[2][kConvWs];
 __device__ unsigned g_conv_tk[2][kConvTk];
 
-static bool conv_split(int role, long M, long N, long K, float** ws, unsigned** tk) {
+// whether the role's GEMM runs split (a pure function of the shape, the knobs and deterministic mode)
+static bool conv_split_plan(long M, long N, long K) {
   if (hopsx_deterministic() || hopsx_disabled("conv_splitk")) return false;
   // only GEMMs with fewer tiles than CUs and a long K: at 392 tiles / K 1,024-2,304 (stage-3 convs at
   // batch 8) the split's workspace round trip cost more than it won (profiles/r5_conv_splitk_b8.txt)
@@ -477,19 +472,17 @@ static bool conv_split(int role, long M, long N, long K, float** ws, unsigned** 
   if (p.split < 2) return false;
   const int bm = p.cfg == 0 ? 128 : (p.cfg == 1 ? 64 : 32);
   const long tiles = ((M + bm - 1) / bm) * ((N + bm - 1) / bm);
-  if (M * N > kConvWs || tiles > kConvTk) return false;
-  static float* wsp = nullptr;
-  static unsigned* tkp = nullptr;
-  if (!wsp) {
-    void *a = nullptr, *b = nullptr;
-    if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_conv_ws)) != hipSuccess ||
-        hipGetSymbolAddress(&b, HIP_SYMBOL(g_conv_tk)) != hipSuccess)
-      return false;
-    wsp = (float*)a;
-    tkp = (unsigned*)b;
-  }
-  *ws = wsp + role * kConvWs;
-  *tk = tkp + role * kConvTk;
+  return M * N <= kConvWs && tiles <= kConvTk;
+}
+
+// the role's workspace and tickets (role 0 forward, 1 dgrad); false: the caller launches the unsplit GEMM
+static bool conv_split_ws(int role, float** ws, unsigned** tk) {
+  static void *wsp = nullptr, *tkp = nullptr;
+  if (!wsp && (hipGetSymbolAddress(&tkp, HIP_SYMBOL(g_conv_tk)) != hipSuccess ||
+               hipGetSymbolAddress(&wsp, HIP_SYMBOL(g_conv_ws)) != hipSuccess))
+    return false;  // (wsp, looked up last, stays null: the next call asks again)
+  *ws = (float*)wsp + role * kConvWs;
+  *tk = (unsigned*)tkp + role * kConvTk;
   return true;
 }
 
@@ -531,13 +524,8 @@ static bool gg_conv_fwd_ok(const void* x, const void* w, const ConvGeom& g) {
   return !(g.C % 8 || g.CO % 8 || ((uintptr_t)x | (uintptr_t)w) % 16 || hopsx_disabled("gg_fwd") || gg_narrow(g, g.CO));
 }
 
-template <class EP>
-static bool gg_conv_fwd(const void* x, const void* w, const ConvGeom& g, const EP& e, hipStream_t st) {
-  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
-  if (!gg_conv_fwd_ok(x, w, g)) return false;
-  const GgDense ws{(const bf16_raw*)w, (long)K, N, K};
-  if (gg_1x1(g)) return launch_gg<true, true>(GgDense{(const bf16_raw*)x, (long)g.C, M, K}, ws, e, M, N, K, false, st);
-  return launch_gg<true, true>(GgIm2col{(const bf16_raw*)x, g, M, K}, ws, e, M, N, K, false, st);
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16 == 0;
 }
 
 // The pixels of parity classes that no tap reaches (a 1x1 / stride-2 conv: all but the (0, 0)
@@ -552,15 +540,21 @@ __global__ __launch_bounds__(256) void dgrad_par_fill_k(bf16_raw* __restrict__ o
   }
 }
 
-// Strided dgrad as sh*sw dense parity-class GEMMs (gemm_glds.h GgDgradParA); classes without taps
-// are filled (dgrad_par_fill_k).  All class plans are checked before anything is launched.
-static bool gg_dgrad_par(const void* dy, const void* w, const ConvGeom& g, const EpiDActBF16& e, hipStream_t st) {
-  if ((g.sh == 1 && g.sw == 1) || g.dh != 1 || g.dw != 1 || g.sh > 4 || g.sw > 4 || hopsx_disabled("dgrad_par"))
-    return false;
-  if ((uintptr_t)e.out % 16 || (uintptr_t)e.add % 16) return false;
+// ---- dgrad on the gg engine.  (This block stands ahead of the forward launchers only so that the kernels keep
+// their numbers within the code object; the order of the blocks has no functional meaning.) ----
+// Strided dgrad as sh*sw dense parity-class GEMMs (gemm_glds.h GgDgradParA); classes without taps are filled
+// (dgrad_par_fill_k).  The plan checks every class, so nothing is launched unless all of them pass.
+struct GgParPlan {
   GgParGeom cls[16];
-  int n = 0;
+  int n = 0;  // classes with taps
   unsigned live = 0;
+};
+
+// n == 0: no plan
+static GgParPlan gg_dgrad_par_plan(const ConvGeom& g) {
+  GgParPlan pp;
+  if ((g.sh == 1 && g.sw == 1) || g.dh != 1 || g.dw != 1 || g.sh > 4 || g.sw > 4 || hopsx_disabled("dgrad_par"))
+    return {};
   for (int py = 0; py < g.sh; ++py)
     for (int px = 0; px < g.sw; ++px) {
       GgParGeom c{};
@@ -572,175 +566,164 @@ static bool gg_dgrad_par(const void* dy, const void* w, const ConvGeom& g, const
       c.nkw = c.kw0 < g.KW ? (g.KW - c.kw0 + g.sw - 1) / g.sw : 0;
       c.Hp = (g.H - py + g.sh - 1) / g.sh;
       c.Wp = (g.W - px + g.sw - 1) / g.sw;
-      if (c.Hp <= 0 || c.Wp <= 0) return false;
-      if (c.nkh <= 0 || c.nkw <= 0) continue;  // no tap reaches this class: filled below
+      if (c.Hp <= 0 || c.Wp <= 0) return {};
+      if (c.nkh <= 0 || c.nkw <= 0) continue;  // no tap reaches this class: filled
       c.fWp.init(c.Wp);
       c.fHWp.init(c.Hp * c.Wp);
       c.fNKW.init(c.nkw);
       GgPlan p;
-      if (!gg_plan((long)g.B * c.Hp * c.Wp, g.C, (long)c.nkh * c.nkw * g.CO, false, p, 1)) return false;
-      live |= 1u << (py * g.sw + px);
-      cls[n++] = c;
+      if (!gg_plan((long)g.B * c.Hp * c.Wp, g.C, (long)c.nkh * c.nkw * g.CO, false, p, 1)) return {};
+      pp.live |= 1u << (py * g.sw + px);
+      pp.cls[pp.n++] = c;
     }
-  if (n == 0) return false;
-  if (n < g.sh * g.sw) {
+  return pp;
+}
+
+// the fill, then (classes) the class GEMMs
+static bool gg_dgrad_par_launch(const void* dy, const void* w, const ConvGeom& g, const EpiDActBF16& e,
+                                const GgParPlan& pp, bool classes, hipStream_t st) {
+  if (pp.n > 0 && pp.n < g.sh * g.sw) {
     const long nch = (long)g.B * g.H * g.W * (g.C / 8);
-    long blocks = (nch + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(dgrad_par_fill_k, dim3((unsigned)blocks), dim3(256), 0, st, e.out, e.add, nch, g.C / 8, g.W,
-                       g.H, g.sh, g.sw, live);
+    const long blocks = std::min((nch + 255) / 256, 4096L);
+    hipLaunchKernelGGL(dgrad_par_fill_k, dim3((unsigned)blocks), dim3(256), 0, st, e.out, e.add, nch, g.C / 8, g.W, g.H,
+                       g.sh, g.sw, pp.live);
   }
-  for (int i = 0; i < n; ++i) {
-    const GgParGeom& c = cls[i];
+  for (int i = 0; classes && i < pp.n; ++i) {
+    const GgParGeom& c = pp.cls[i];
     const int M = g.B * c.Hp * c.Wp, K = c.nkh * c.nkw * g.CO;
     const GgDgradParA as{(const bf16_raw*)dy, g, c, M, K};
     const GgWeightTPar bs{(const bf16_raw*)w, g, c, K, g.C};
     const EpiDgradParBF16 ep{e.out, e.y, e.act, e.colsum, e.add, g.C, g.H, g.W, c.Wp, c.Hp * c.Wp,
                              c.py, c.px, g.sh, g.sw, c.fWp, c.fHWp};
-    if (!launch_gg<true, false>(as, bs, ep, M, g.C, K, false, st, 1)) return false;  // (plans checked above)
+    if (!launch_gg<true, false>(as, bs, ep, M, g.C, K, false, st, 1)) return false;  // (the plan checked it)
   }
   return true;
 }
 
-static bool gg_conv_dgrad(const void* dy, const void* w, const ConvGeom& g, const EpiDActBF16& e, hipStream_t st) {
+// CONV_GG_DENSE / CONV_GG_GATHER, the gg routes both dgrad launchers have (false: the engine refused)
+template <class EP>
+static bool gg_dgrad_gemm(int route, const void* dy, const GgWeightT& ws, const ConvGeom& g, const EP& e, hipStream_t st) {
   const int M = g.B * g.H * g.W, N = g.C, K = g.KH * g.KW * g.CO;
-  if (g.C % 8 || g.CO % 8 || ((uintptr_t)dy | (uintptr_t)w) % 16 || hopsx_disabled("gg_dgrad") || gg_narrow(g, N))
-    return false;
-  // stride > 1: the dense parity-class GEMMs instead of the zero-inserting gather (when the whole
-  // shape would take gg; the class GEMMs are launched however few workgroups each gives)
-  {
-    GgPlan p;
-    if (e.ldo == g.C && (!e.y || e.ldy == g.C) && gg_plan(M, N, K, false, p) && gg_dgrad_par(dy, w, g, e, st))
-      return true;
-  }
-  const GgWeightT ws{(const bf16_raw*)w, g, K, N};
-  if (g.KH == 1 && g.KW == 1 && g.ph == 0 && g.pw == 0 && (g.sh > 1 || g.sw > 1) && g.H == g.OH * g.sh &&
-      g.W == g.OW * g.sw && !e.colsum && !hopsx_disabled("dgrad_scatter")) {
-    const int Mo = g.B * g.OH * g.OW;
+  return route == CONV_GG_DENSE
+             ? launch_gg<true, false>(GgDense{(const bf16_raw*)dy, (long)g.CO, M, K}, ws, e, M, N, K, false, st)
+             : launch_gg<true, false>(GgDgradA{(const bf16_raw*)dy, g, M, K}, ws, e, M, N, K, false, st);
+}
+
+// every gg route of hopsx_conv2d_dgrad: the two above and the parity and scatter epilogues, which only it has
+static bool gg_dgrad_launch(int route, const void* dy, const GgWeightT& ws, const ConvGeom& g, const EpiDActBF16& e,
+                            const GgParPlan& pp, hipStream_t st) {
+  if (route == CONV_GG_PAR) return gg_dgrad_par_launch(dy, ws.w, g, e, pp, true, st);
+  if (route == CONV_GG_SCATTER) {
+    const int Mo = g.B * g.OH * g.OW, N = g.C, K = g.KH * g.KW * g.CO;
     EpiDgradScatterBF16 es{e.out, e.y, e.act, e.add, g.C, g.W, g.OW, g.OH * g.OW, g.sh, g.sw, {}, {}, nullptr};
     es.fOW.init(g.OW);
     es.fOHW.init(g.OH * g.OW);
     return launch_gg<true, false>(GgDense{(const bf16_raw*)dy, (long)g.CO, Mo, K}, ws, es, Mo, N, K, false, st);
   }
-  if (gg_1x1(g))
-    return launch_gg<true, false>(GgDense{(const bf16_raw*)dy, (long)g.CO, M, K}, ws, e, M, N, K, false, st);
-  return launch_gg<true, false>(GgDgradA{(const bf16_raw*)dy, g, M, K}, ws, e, M, N, K, false, st);
+  return gg_dgrad_gemm(route, dy, ws, g, e, st);
+}
+
+// ---- forward: the route, decided here once for the three launchers and for hopsx_conv2d_fwd_path ----
+// kind (ops_api.h): what the caller's epilogue permits.  Only a plain bf16 store has the direct input-layer kernel;
+// the MFMA kernel has no column sums; an fp32 store stays on gemm_core.h's engine, unsplit; the BN statistics need
+// CO on the vector BN path and, past the MFMA kernel, C % 8 == 0.  x / w / out: only their alignment is used.
+enum ConvFwdKind : int { FWD_STORE = 0, FWD_COLSUM, FWD_F32, FWD_RES, FWD_BNSTATS };
+
+static int conv_fwd_route(const int* geom, const ConvGeom& g, const void* x, const void* w, const void* out, int kind) {
+  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
+  if (kind < FWD_STORE || kind > FWD_BNSTATS) return -2;
+  if (kind == FWD_BNSTATS && (hopsx_disabled("bnstats") || !hopsx_bn_prestats_ok(g.CO))) return -2;
+  if (kind == FWD_STORE && direct_ok(g) && (uintptr_t)out % 8 == 0) return CONV_DIRECT;
+  if (kind != FWD_COLSUM && kind != FWD_F32 && hopsx_conv_fwd_mfma_ok(geom) && !gg_big_spatial(geom) &&
+      aligned16(x, w, out))
+    return CONV_MFMA;
+  if (kind == FWD_BNSTATS && g.C % 8 != 0) return -2;
+  if (kind == FWD_F32) return CONV_GEMM;
+  GgPlan p;
+  if (gg_conv_fwd_ok(x, w, g) && gg_takes(M, N, K, false, p)) return CONV_GG;
+  return conv_split_plan(M, N, K) ? CONV_SPLITK : CONV_GEMM;
+}
+
+extern "C" int hopsx_conv2d_fwd_path(const int* geom, int kind) {
+  return conv_fwd_route(geom, conv_geom_from(geom), nullptr, nullptr, nullptr, kind);
+}
+
+// The GEMM routes of the forward.  e: the caller's epilogue; fin: the same epilogue as the split-K finish (cnt is
+// filled in here) and TK the ticket epilogue that carries it; TK = void: an epilogue with neither gg nor finish.
+template <class TK, class EP>
+static int conv_fwd_launch(int route, const void* x, const void* w, const ConvGeom& g, const EP& e, SplitFinish fin,
+                           hipStream_t st) {
+  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
+  Im2colLoader al{(const bf16_raw*)x, g, (g.C % 8 == 0) && ((uintptr_t)x % 16 == 0)};
+  DenseLoader bl{(const bf16_raw*)w, K, is_vec_ok(w, K)};
+  if constexpr (!std::is_void_v<TK>) {
+    if (route == CONV_GG) {
+      const GgDense ws{(const bf16_raw*)w, (long)K, N, K};
+      const bool ok = gg_1x1(g) ? launch_gg<true, true>(GgDense{(const bf16_raw*)x, (long)g.C, M, K}, ws, e, M, N, K, false, st)
+                                : launch_gg<true, true>(GgIm2col{(const bf16_raw*)x, g, M, K}, ws, e, M, N, K, false, st);
+      return ok ? (int)hipGetLastError() : -6;  // (-6: the engine refused what the route asked gg_takes for)
+    }
+    float* ws;
+    if (route == CONV_SPLITK && conv_split_ws(0, &ws, &fin.cnt)) {
+      TK t{};
+      static_cast<EpiAtomicTicket&>(t) = EpiAtomicTicket{ws, N, 1.f, nullptr, fin};
+      launch_gemm<true, true>(al, bl, t, M, N, K, true, st);
+      return (int)hipGetLastError();
+    }
+  }
+  launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
+  return (int)hipGetLastError();
 }
 
 extern "C" int hopsx_conv2d_fwd(const void* x, const void* w, const int* geom, int epi, void* out,
                                 const float* bias, int act, float* colsum, float xscale, float xshift,
                                 hipStream_t st) {
-  ConvGeom g = make_geom(geom);
+  const ConvGeom g = conv_geom_from(geom);
   const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
-  const bool direct = epi == EPI_STORE_BF16 && !colsum && direct_ok(g) && ((uintptr_t)out % 8 == 0);
-  if (xscale != 0.f && !direct) return -3;  // uint8 inputs are only fused into the direct kernel
-  if (direct) {
-    long total = (long)M * (N / 4);
-    long grid = (total + 255) / 256;
-    if (grid > 4096) grid = 4096;
+  const int kind = epi == EPI_STORE_F32 ? FWD_F32 : (epi != EPI_STORE_BF16 ? -1 : (colsum ? FWD_COLSUM : FWD_STORE));
+  const int route = conv_fwd_route(geom, g, x, w, out, kind);
+  if (xscale != 0.f && route != CONV_DIRECT) return -3;  // uint8 inputs are only fused into the direct kernel
+  if (route < 0) return route;
+  if (route == CONV_DIRECT) {
+    const long grid = std::min(((long)M * (N / 4) + 255) / 256, 4096L);
     hipLaunchKernelGGL(conv_direct_fwd_k, dim3(grid), dim3(256), (size_t)K * N * sizeof(float), st, x, xscale,
                        xshift, (const bf16_raw*)w, bias, (bf16_raw*)out, g, act);
     return (int)hipGetLastError();
   }
-  if (epi == EPI_STORE_BF16 && !colsum && hopsx_conv_fwd_mfma_ok(geom) && !gg_big_spatial(geom) && ((uintptr_t)x % 16 == 0) &&
-      ((uintptr_t)w % 16 == 0) && ((uintptr_t)out % 16 == 0))
-    return hopsx_conv2d_fwd_mfma(x, w, geom, out, bias, act, st);
-  Im2colLoader al{(const bf16_raw*)x, g, (g.C % 8 == 0) && ((uintptr_t)x % 16 == 0)};
-  DenseLoader bl{(const bf16_raw*)w, K, is_vec_ok(w, K)};
-  if (epi == EPI_STORE_BF16) {
-    EpiStoreBF16 e{(bf16_raw*)out, N, bias, 1.f, act, colsum};
-    if (gg_conv_fwd(x, w, g, e, st)) return (int)hipGetLastError();
-    float* ws;
-    unsigned* tk;
-    if (conv_split(0, M, N, K, &ws, &tk)) {
-      const SplitFinish f{tk, kEpiStoreBF16, out, N, bias, 1.f, 0.f, act, nullptr, 0, colsum, nullptr};
-      launch_gemm<true, true>(al, bl, EpiAtomicTicket{ws, N, 1.f, nullptr, f}, M, N, K, true, st);
-      return (int)hipGetLastError();
-    }
-    launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
-  } else if (epi == EPI_STORE_F32) {
-    EpiStoreF32 e{(float*)out, N, bias, 1.f, 0.f, act, colsum};
-    launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
-  } else {
-    return -2;
+  if (route == CONV_MFMA) return hopsx_conv2d_fwd_mfma(x, w, geom, out, bias, act, st);
+  if (kind != FWD_F32) {
+    const SplitFinish f{nullptr, kEpiStoreBF16, out, N, bias, 1.f, 0.f, act, nullptr, 0, colsum, nullptr};
+    return conv_fwd_launch<EpiAtomicTicket>(route, x, w, g, EpiStoreBF16{(bf16_raw*)out, N, bias, 1.f, act, colsum}, f, st);
   }
-  return (int)hipGetLastError();
+  return conv_fwd_launch<void>(route, x, w, g, EpiStoreF32{(float*)out, N, bias, 1.f, 0.f, act, colsum}, {}, st);
 }
 
-// ---- forward with a residual (frozen inference: BatchNorm folded into w / bias, the block's shortcut added
-// before the activation).  The route is hopsx_conv2d_fwd's for a bf16 store without column sums, decided here
-// once for the launcher and for the query; the direct input-layer kernel is not among them.
-enum ConvResRoute : int { RES_MFMA = 0, RES_GG = 1, RES_GEMM = 2, RES_SPLITK = 3 };
-
-// x / w / out: the operands (the query passes aligned dummies); the same tests, in the same order, as
-// hopsx_conv2d_fwd's bf16-store branch
-static int conv_res_route(const int* geom, const ConvGeom& g, const void* x, const void* w, const void* out,
-                          float** ws, unsigned** tk) {
-  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
-  if (hopsx_conv_fwd_mfma_ok(geom) && !gg_big_spatial(geom) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0))
-    return RES_MFMA;
-  GgPlan p;
-  if (gg_conv_fwd_ok(x, w, g) && gg_takes(M, N, K, false, p)) return RES_GG;
-  return conv_split(0, M, N, K, ws, tk) ? RES_SPLITK : RES_GEMM;
-}
-
-extern "C" int hopsx_conv2d_fwd_res_path(const int* geom) {
-  const ConvGeom g = make_geom(geom);
-  float* ws;
-  unsigned* tk;
-  return conv_res_route(geom, g, nullptr, nullptr, nullptr, &ws, &tk);
-}
-
+// Frozen inference: BatchNorm folded into w / bias, the block's shortcut added before the activation
 extern "C" int hopsx_conv2d_fwd_res(const void* x, const void* w, const int* geom, void* out, const float* bias,
                                     int act, const void* residual, hipStream_t st) {
   if (!residual) return hopsx_conv2d_fwd(x, w, geom, EPI_STORE_BF16, out, bias, act, nullptr, 0.f, 0.f, st);
   if (act != ACT_NONE && act != ACT_RELU) return -2;
-  const ConvGeom g = make_geom(geom);
-  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
+  const ConvGeom g = conv_geom_from(geom);
+  const int M = g.B * g.OH * g.OW, N = g.CO;
   if ((uintptr_t)residual % 16) return -4;
   const uintptr_t ro = (uintptr_t)residual, oo = (uintptr_t)out, nb = (uintptr_t)M * N * sizeof(bf16_raw);
   if (ro < oo + nb && oo < ro + nb) return -5;
-  float* ws = nullptr;
-  unsigned* tk = nullptr;
-  const int route = conv_res_route(geom, g, x, w, out, &ws, &tk);
-  if (route == RES_MFMA) return hopsx_conv2d_fwd_mfma_res(x, w, geom, out, bias, act, residual, st);
+  const int route = conv_fwd_route(geom, g, x, w, out, FWD_RES);
+  if (route == CONV_MFMA) return hopsx_conv2d_fwd_mfma_res(x, w, geom, out, bias, act, residual, st);
   const EpiStoreResBF16 e{(bf16_raw*)out, N, bias, 1.f, act, nullptr, (const bf16_raw*)residual};
-  if (route == RES_GG) return gg_conv_fwd(x, w, g, e, st) ? (int)hipGetLastError() : -6;  // (the plan said yes)
-  Im2colLoader al{(const bf16_raw*)x, g, (g.C % 8 == 0) && ((uintptr_t)x % 16 == 0)};
-  DenseLoader bl{(const bf16_raw*)w, K, is_vec_ok(w, K)};
-  if (route == RES_SPLITK) {
-    const SplitFinish f{tk, kEpiStoreResBF16, out, N, bias, 1.f, 0.f, act, nullptr, 0, nullptr,
-                        (const bf16_raw*)residual};
-    launch_gemm<true, true>(al, bl, EpiAtomicTicketRes{{ws, N, 1.f, nullptr, f}}, M, N, K, true, st);
-    return (int)hipGetLastError();
-  }
-  launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
-  return (int)hipGetLastError();
+  const SplitFinish f{nullptr, kEpiStoreResBF16, out, N, bias, 1.f, 0.f, act, nullptr, 0, nullptr, e.res};
+  return conv_fwd_launch<EpiAtomicTicketRes>(route, x, w, g, e, f, st);
 }
 
 extern "C" int hopsx_conv2d_fwd_bnstats(const void* x, const void* w, const int* geom, void* out, float* bnacc,
                                         hipStream_t st) {
-  if (!bnacc || hopsx_disabled("bnstats") || !hopsx_bn_prestats_ok(geom[6])) return -2;
-  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out) % 16 != 0) return -2;
-  if (hopsx_conv_fwd_mfma_ok(geom) && !gg_big_spatial(geom))
-    return hopsx_conv2d_fwd_mfma_ex(x, w, geom, out, nullptr, 0, bnacc, st);
-  ConvGeom g = make_geom(geom);
-  if (g.C % 8 != 0) return -2;
-  const int M = g.B * g.OH * g.OW, N = g.CO, K = g.KH * g.KW * g.C;
-  Im2colLoader al{(const bf16_raw*)x, g, 1};
-  DenseLoader bl{(const bf16_raw*)w, K, is_vec_ok(w, K)};
-  EpiBnStatsBF16 e{(bf16_raw*)out, N, bnacc};
-  if (gg_conv_fwd(x, w, g, e, st)) return (int)hipGetLastError();
-  float* ws;
-  unsigned* tk;
-  if (conv_split(0, M, N, K, &ws, &tk)) {
-    const SplitFinish f{tk, kEpiBnStatsBF16, out, N, nullptr, 1.f, 0.f, 0, nullptr, 0, bnacc, nullptr};
-    launch_gemm<true, true>(al, bl, EpiAtomicTicket{ws, N, 1.f, nullptr, f}, M, N, K, true, st);
-    return (int)hipGetLastError();
-  }
-  launch_gemm<true, true>(al, bl, e, M, N, K, false, st);
-  return (int)hipGetLastError();
+  if (!bnacc || !aligned16(x, w, out)) return -2;
+  const ConvGeom g = conv_geom_from(geom);
+  const int route = conv_fwd_route(geom, g, x, w, out, FWD_BNSTATS);
+  if (route < 0) return route;
+  if (route == CONV_MFMA) return hopsx_conv2d_fwd_mfma_ex(x, w, geom, out, nullptr, 0, bnacc, st);
+  const SplitFinish f{nullptr, kEpiBnStatsBF16, out, g.CO, nullptr, 1.f, 0.f, 0, nullptr, 0, bnacc, nullptr};
+  return conv_fwd_launch<EpiAtomicTicket>(route, x, w, g, EpiBnStatsBF16{(bf16_raw*)out, g.CO, bnacc}, f, st);
 }
 
 extern "C" int hopsx_conv2d_fwd_bnstats_inbn(const void* z, void* a, const void* w, const int* geom, void* out,
@@ -754,68 +737,105 @@ extern "C" int hopsx_conv2d_fwd_bnstats_inbn(const void* z, void* a, const void*
                                     momentum, eps, act, st);
 }
 
-// dX = conv_transpose(dY, W).  If `yprev` is given, the result is multiplied by
-// act'(yprev) — the backward of the activation that produced this conv's input
-// — and `colsum` receives that layer's bias gradient.
-extern "C" int hopsx_conv2d_dgrad(const void* dy, const void* w, const int* geom, void* dx, const void* yprev,
-                                  int act, float* colsum, const void* y, int yact, const void* addend,
-                                  hipStream_t st) {
-  if (!addend && hopsx_conv_dgrad_mfma_ok(geom) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)y % 16 == 0) &&
-      ((uintptr_t)dx % 16 == 0) && ((uintptr_t)yprev % 16 == 0))
-    return hopsx_conv2d_dgrad_mfma(dy, w, geom, dx, yprev, act, colsum, y, yact, st);
-  ConvGeom g = make_geom(geom);
+// ---- dgrad: dX = conv_transpose(dY, W); the route, decided here once for both launchers and the query ----
+// flags: what the caller is and has (the first four are hopsx_conv2d_dgrad_path's) and which operand groups are
+// not 16-B aligned.  DG_BN = hopsx_conv2d_dgrad_bn, whose epilogue has no parity / scatter form and no finish.
+// DG_MIS_*: dy | y | dx | yprev, dy | w, dx | addend.
+enum ConvDgradFlag : int { DG_Y = 1, DG_ADDEND = 2, DG_BN = 4, DG_COLSUM = 8, DG_MIS_MFMA = 16, DG_MIS_GG = 32, DG_MIS_PAR = 64 };
+
+// pp: the parity plan where it passed: with CONV_GG_PAR, and, the gg engine off, with the GEMM route that follows
+static int conv_dgrad_route(const int* geom, const ConvGeom& g, int flags, GgParPlan& pp) {
   const int M = g.B * g.H * g.W, N = g.C, K = g.KH * g.KW * g.CO;
-  ConvDgradALoader al{(const bf16_raw*)dy, g,
-                      (g.CO % 8 == 0) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)y % 16 == 0),
-                      (const bf16_raw*)y, yact};
-  ConvWeightTLoader bl{(const bf16_raw*)w, g, (g.C % 8 == 0) && ((uintptr_t)w % 16 == 0)};
-  EpiDActBF16 e{(bf16_raw*)dx, N, (const bf16_raw*)yprev, N, act, colsum, (const bf16_raw*)addend};
-  if (!y && gg_conv_dgrad(dy, w, g, e, st)) return (int)hipGetLastError();
-  float* ws;
-  unsigned* tk;
-  if (conv_split(1, M, N, K, &ws, &tk)) {
-    const SplitFinish f{tk, kEpiDActBF16, dx, N, nullptr, 1.f, 0.f, act, (const bf16_raw*)yprev, N, colsum,
-                        (const bf16_raw*)addend};
-    launch_gemm<true, false>(al, bl, EpiAtomicTicket{ws, N, 1.f, nullptr, f}, M, N, K, true, st);
-    return (int)hipGetLastError();
+  const bool bn = flags & DG_BN;
+  pp = GgParPlan{};
+  if (bn) {
+    if (hopsx_disabled("bn_dgrad_sums") || g.sh != 1 || g.sw != 1 || g.C % 8 || g.CO % 8 || !hopsx_bn_prestats_ok(g.C))
+      return -2;
+    if (hopsx_conv_dgrad_mfma_bn_ok(geom)) return CONV_MFMA;
+  } else if (!(flags & (DG_ADDEND | DG_MIS_MFMA)) && hopsx_conv_dgrad_mfma_ok(geom)) {
+    return CONV_MFMA;
   }
-  launch_gemm<true, false>(al, bl, e, M, N, K, false, st);
+  // (bn: a shape whose plain dgrad would split K keeps the plain dgrad)
+  const int rest = !conv_split_plan(M, N, K) ? CONV_GEMM : (bn ? -2 : CONV_SPLITK);
+  if ((flags & (DG_Y | DG_MIS_GG)) || g.C % 8 || g.CO % 8 || hopsx_disabled("gg_dgrad") || gg_narrow(g, N)) return rest;
+  GgPlan p;
+  // stride > 1: the dense parity-class GEMMs instead of the zero-inserting gather (when the whole
+  // shape would take gg; the class GEMMs are launched however few workgroups each gives)
+  if (!bn && !(flags & DG_MIS_PAR) && gg_plan(M, N, K, false, p) && (pp = gg_dgrad_par_plan(g)).n > 0 && gg_on())
+    return CONV_GG_PAR;
+  if (g.KH == 1 && g.KW == 1 && g.ph == 0 && g.pw == 0 && (g.sh > 1 || g.sw > 1) && g.H == g.OH * g.sh &&
+      g.W == g.OW * g.sw && !(flags & DG_COLSUM) && !hopsx_disabled("dgrad_scatter"))
+    return gg_takes(g.B * g.OH * g.OW, N, K, false, p) ? CONV_GG_SCATTER : rest;
+  if (!gg_takes(M, N, K, false, p)) return rest;
+  return gg_1x1(g) ? CONV_GG_DENSE : CONV_GG_GATHER;
+}
+
+extern "C" int hopsx_conv2d_dgrad_path(const int* geom, int flags) {
+  GgParPlan pp;
+  return conv_dgrad_route(geom, conv_geom_from(geom), flags & (DG_Y | DG_ADDEND | DG_BN | DG_COLSUM), pp);
+}
+
+// gemm_core.h's engine for CONV_SPLITK / CONV_GEMM (fin: e as the split-K finish, cnt filled in here; the bn
+// caller never gets CONV_SPLITK)
+template <class EP>
+static int conv_dgrad_gemm(int route, const void* dy, const void* w, const void* y, int yact, const ConvGeom& g,
+                           const EP& e, SplitFinish fin, hipStream_t st) {
+  const int M = g.B * g.H * g.W, N = g.C, K = g.KH * g.KW * g.CO;
+  ConvDgradALoader al{(const bf16_raw*)dy, g, (g.CO % 8 == 0) && aligned16(dy, y), (const bf16_raw*)y, yact};
+  ConvWeightTLoader bl{(const bf16_raw*)w, g, (g.C % 8 == 0) && ((uintptr_t)w % 16 == 0)};
+  float* ws;
+  if (route == CONV_SPLITK && conv_split_ws(1, &ws, &fin.cnt))
+    launch_gemm<true, false>(al, bl, EpiAtomicTicket{ws, N, 1.f, nullptr, fin}, M, N, K, true, st);
+  else
+    launch_gemm<true, false>(al, bl, e, M, N, K, false, st);
   return (int)hipGetLastError();
 }
 
-// dX of a conv whose input x is a training BatchNorm's output consumed only by this conv: the epilogue
-// adds `addend` (a shortcut's gradient of x), masks by act_prev'(yprev = x), stores g and reduces the
-// BN's backward column sums (sum g, sum g * xhat) into the replica rows bnacc[HOPSX_BN_NREP][2C]
-// (gemm_core.h EpiDgradBnBF16; conv_mfma.hip DgradArgs bnacc for the direct MFMA shapes).  Stride-1
-// convs on the direct MFMA kernel, the gg engine (1x1 and implicit-GEMM gathers) or gemm_core.h's
-// engine without split-K; anything else (strided parity GEMMs, split-K) returns -2 with nothing
-// launched and the caller runs the plain dgrad + the full BN backward.
+// If `yprev` is given, the result is multiplied by act'(yprev) — the backward of the activation that
+// produced this conv's input — and `colsum` receives that layer's bias gradient.
+extern "C" int hopsx_conv2d_dgrad(const void* dy, const void* w, const int* geom, void* dx, const void* yprev,
+                                  int act, float* colsum, const void* y, int yact, const void* addend,
+                                  hipStream_t st) {
+  const ConvGeom g = conv_geom_from(geom);
+  const int N = g.C, K = g.KH * g.KW * g.CO;
+  const int flags = (y ? DG_Y : 0) | (addend ? DG_ADDEND : 0) | (colsum ? DG_COLSUM : 0) |
+                    (aligned16(dy, y, dx, yprev) ? 0 : DG_MIS_MFMA) | (aligned16(dy, w) ? 0 : DG_MIS_GG) |
+                    (aligned16(dx, addend) ? 0 : DG_MIS_PAR);
+  GgParPlan pp;
+  const int route = conv_dgrad_route(geom, g, flags, pp);
+  if (route == CONV_MFMA) return hopsx_conv2d_dgrad_mfma(dy, w, geom, dx, yprev, act, colsum, y, yact, st);
+  const EpiDActBF16 e{(bf16_raw*)dx, N, (const bf16_raw*)yprev, N, act, colsum, (const bf16_raw*)addend};
+  if (route >= CONV_GG_PAR)  // (-6: the engine refused what the route asked gg_takes for)
+    return gg_dgrad_launch(route, dy, GgWeightT{(const bf16_raw*)w, g, K, N}, g, e, pp, st) ? (int)hipGetLastError() : -6;
+  // kept as it was before the route was a value: with the gg engine off (HOPSX_DISABLE=gg, deterministic mode) a
+  // shape whose parity plan passes still gets the fill launch, and the GEMM below then writes every pixel
+  gg_dgrad_par_launch(dy, w, g, e, pp, false, st);
+  const SplitFinish f{nullptr, kEpiDActBF16, dx, N, nullptr, 1.f, 0.f, act, e.y, N, colsum, e.add};
+  return conv_dgrad_gemm(route, dy, w, y, yact, g, e, f, st);
+}
+
+// dX of a conv whose input x is a training BatchNorm's output consumed only by this conv: the epilogue adds `addend`
+// (a shortcut's gradient of x), masks by act_prev'(yprev = x), stores g and reduces the BN's backward column sums (sum
+// g, sum g * xhat) into the replica rows bnacc[HOPSX_BN_NREP][2C] (gemm_core.h EpiDgradBnBF16; conv_mfma.hip DgradArgs
+// bnacc).  The routes conv_dgrad_route leaves a bn caller; anything else (a stride, a shape whose plain dgrad splits K)
+// returns -2 with nothing launched and the caller runs the plain dgrad + the full BN backward.
 extern "C" int hopsx_conv2d_dgrad_bn(const void* dy, const void* w, const int* geom, void* dx, const void* yprev,
                                      int act_prev, const void* addend, const void* bnz, const float* bnmean,
                                      const float* bnrstd, float* bnacc, hipStream_t st) {
-  ConvGeom g = make_geom(geom);
-  if (!bnacc || !bnz || !bnmean || !bnrstd || hopsx_disabled("bn_dgrad_sums") || g.sh != 1 || g.sw != 1 ||
-      g.C % 8 || g.CO % 8 || !hopsx_bn_prestats_ok(g.C) ||
-      ((uintptr_t)dy | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)yprev | (uintptr_t)addend | (uintptr_t)bnz) % 16)
-    return -2;
-  const int r = hopsx_conv2d_dgrad_mfma_bn(dy, w, geom, dx, yprev, act_prev, addend, bnz, bnmean, bnrstd, bnacc, st);
-  if (r != -2) return r;
-  const int M = g.B * g.H * g.W, N = g.C, K = g.KH * g.KW * g.CO;
-  const EpiDgradBnBF16 e{(bf16_raw*)dx, N, (const bf16_raw*)yprev, act_prev, (const bf16_raw*)addend,
+  if (!bnacc || !bnz || !bnmean || !bnrstd || !aligned16(dy, w, dx, yprev) || !aligned16(addend, bnz)) return -2;
+  const ConvGeom g = conv_geom_from(geom);
+  GgParPlan pp;
+  const int route = conv_dgrad_route(geom, g, DG_BN | (addend ? DG_ADDEND : 0), pp);
+  if (route < 0) return route;
+  if (route == CONV_MFMA)
+    return hopsx_conv2d_dgrad_mfma_bn(dy, w, geom, dx, yprev, act_prev, addend, bnz, bnmean, bnrstd, bnacc, st);
+  const EpiDgradBnBF16 e{(bf16_raw*)dx, g.C, (const bf16_raw*)yprev, act_prev, (const bf16_raw*)addend,
                          (const bf16_raw*)bnz, bnmean, bnrstd, bnacc};
-  if (!hopsx_disabled("gg_dgrad") && !gg_narrow(g, N)) {
-    const GgWeightT ws{(const bf16_raw*)w, g, K, N};
-    if (gg_1x1(g) ? launch_gg<true, false>(GgDense{(const bf16_raw*)dy, (long)g.CO, M, K}, ws, e, M, N, K, false, st)
-                  : launch_gg<true, false>(GgDgradA{(const bf16_raw*)dy, g, M, K}, ws, e, M, N, K, false, st))
-      return (int)hipGetLastError();
-  }
-  float* sws;
-  unsigned* stk;
-  if (conv_split(1, M, N, K, &sws, &stk)) return -2;  // the plain dgrad would split K: keep it
-  ConvDgradALoader al{(const bf16_raw*)dy, g, 1, nullptr, 0};
-  ConvWeightTLoader bl{(const bf16_raw*)w, g, 1};
-  launch_gemm<true, false>(al, bl, e, M, N, K, false, st);
-  return (int)hipGetLastError();
+  if (route >= CONV_GG_PAR)
+    return gg_dgrad_gemm(route, dy, GgWeightT{(const bf16_raw*)w, g, g.KH * g.KW * g.CO, g.C}, g, e, st)
+               ? (int)hipGetLastError()
+               : -6;
+  return conv_dgrad_gemm(route, dy, w, nullptr, 0, g, e, SplitFinish{}, st);
 }
 
 // dW[co][k] += sum_m dY[m][co] * im2col(X)[m][k]; db[co] += sum_m dY[m][co] when colsum given
@@ -832,7 +852,7 @@ static bool smallk_ok(const ConvGeom& g, const void* dy, const void* y, const fl
 extern "C" int hopsx_conv2d_wgrad(const void* dy, const void* x, const int* geom, float* dw, float* dbias,
                                   const void* y, int yact, float* ws, long ws_elems, float xscale, float xshift,
                                   unsigned* counter, hipStream_t st) {
-  ConvGeom g = make_geom(geom);
+  const ConvGeom g = conv_geom_from(geom);
   const int M = g.CO, N = g.KH * g.KW * g.C, K = g.B * g.OH * g.OW;
   // one-channel input layers: the pixel-range kernel (conv_wgrad_c1_k)
   if (g.C == 1 && N <= 25 && (g.CO == 8 || g.CO == 16 || g.CO == 32 || g.CO == 64) && (uintptr_t)dy % 16 == 0 &&

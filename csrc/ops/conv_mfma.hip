@@ -1203,11 +1203,7 @@ extern "C" int hopsx_conv2d_fwd_mfma(const void* x, const void* w, const int* ge
 // with bnacc): out = act(conv + bias + res) (conv_fwd_mfma_k RES)
 static int fwd_mfma_impl(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
                          float* bnacc, const void* res, hipStream_t st) {
-  ConvGeom g;
-  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
-  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
-  g.dh = geom[13]; g.dw = geom[14];
-  g.init_div();
+  const ConvGeom g = conv_geom_from(geom);
   const int K = g.KH * g.KW * g.C;
   const int KS = cm_ks5((K + 31) / 32);
   const long M = (long)g.B * g.OH * g.OW;
@@ -1267,11 +1263,7 @@ extern "C" int hopsx_conv2d_fwd_mfma_inbn(const void* z, void* a, const void* w,
   if (!hopsx_conv_fwd_mfma_ok(geom) || hopsx_disabled("bn_fold") || !bnacc || !inacc || bnacc == inacc || !a ||
       !mean_out || !rstd_out || (act != ACT_NONE && act != ACT_RELU))
     return -2;
-  ConvGeom g;
-  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
-  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
-  g.dh = geom[13]; g.dw = geom[14];
-  g.init_div();
+  const ConvGeom g = conv_geom_from(geom);
   if (g.sh != 1 || g.sw != 1 || g.dh != 1 || g.dw != 1 || g.OH < 1 || g.OW < 1) return -2;
   if (32 % g.C != 0) return -2;  // C in {8, 16, 32}: a lane's channels are the same at every tap (InBn)
   if (((uintptr_t)z | (uintptr_t)a | (uintptr_t)w | (uintptr_t)out) % 16 != 0) return -2;
@@ -1308,15 +1300,6 @@ extern "C" int hopsx_conv2d_fwd_mfma_inbn(const void* z, void* a, const void* w,
   return (int)hipGetLastError();
 }
 
-static ConvGeom cm_geom(const int* geom) {
-  ConvGeom g;
-  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
-  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
-  g.dh = geom[13]; g.dw = geom[14];
-  g.init_div();
-  return g;
-}
-
 // the dgrad of this conv (geom) can carry the wgrad of the input layer feeding it (geom0)
 bool hopsx_conv_dgrad_fused_wgrad_ok(const int* geom, const int* geom0) {
   const int K0 = geom0[7] * geom0[8] * geom0[3];
@@ -1343,12 +1326,27 @@ extern "C" int hopsx_conv2d_dgrad_mfma_ex(const void* dy, const void* w, const i
                          nullptr, nullptr, nullptr, nullptr, st);
 }
 
+// LDS of conv_dgrad_mfma_k (weight image, staging rows, the column-sum partials: bias gradient, K0 fused taps, bn:
+// sum g * xhat; tap table) and gfx950's limit per workgroup (C = 128 at K = 512 with the BN sums: 161 KB)
+static size_t dgrad_mfma_lds(const ConvGeom& g, int KS, int K0, bool bn) {
+  return (size_t)(g.C * cm_rs(KS * 4) * 8 + CM_WAVES * 16 * g.C) * sizeof(bf16_raw) +
+         (size_t)CM_RSLOTS * g.C * (1 + K0 + (bn ? 1 : 0)) * sizeof(float) + (size_t)KS * 4 * 16;
+}
+constexpr size_t kDgradMfmaLdsMax = 160u * 1024u;
+
+// the shapes hopsx_conv2d_dgrad_mfma_bn takes (conv.hip conv_dgrad_route asks before it names the MFMA route)
+bool hopsx_conv_dgrad_mfma_bn_ok(const int* geom) {
+  if (!hopsx_conv_dgrad_mfma_ok(geom)) return false;
+  const ConvGeom g = conv_geom_from(geom);
+  return dgrad_mfma_lds(g, cm_ks5((g.KH * g.KW * g.CO + 31) / 32), 0, true) <= kDgradMfmaLdsMax;
+}
+
 // the direct MFMA dgrad with the input BN's backward column sums in its epilogue (DgradArgs bnacc) and an
 // optional shortcut gradient added before the act'(yprev) mask; -2: not this kernel's shape (nothing launched)
 extern "C" int hopsx_conv2d_dgrad_mfma_bn(const void* dy, const void* w, const int* geom, void* dx, const void* yprev,
                                           int act_prev, const void* addend, const void* bnz, const float* bnmean,
                                           const float* bnrstd, float* bnacc, hipStream_t st) {
-  if (!hopsx_conv_dgrad_mfma_ok(geom) || !bnacc || !bnz || !bnmean || !bnrstd ||
+  if (!hopsx_conv_dgrad_mfma_bn_ok(geom) || !bnacc || !bnz || !bnmean || !bnrstd ||
       ((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)yprev | (uintptr_t)addend | (uintptr_t)bnz) % 16)
     return -2;
   return dgrad_mfma_impl(dy, w, geom, dx, yprev, act_prev, nullptr, nullptr, 0, nullptr, nullptr, 0.f, 0.f, nullptr,
@@ -1361,9 +1359,9 @@ static int dgrad_mfma_impl(const void* dy, const void* w, const int* geom, void*
                            const float* bnrstd, float* bnacc, hipStream_t st) {
   const bool fused = geom0 != nullptr;
   if (fused && (!hopsx_conv_dgrad_fused_wgrad_ok(geom, geom0) || !yprev || !colsum || !dw0 || !x0)) return -4;
-  ConvGeom g0 = fused ? cm_geom(geom0) : ConvGeom{};
+  ConvGeom g0 = fused ? conv_geom_from(geom0) : ConvGeom{};
   const int K0 = fused ? geom0[7] * geom0[8] : 0;
-  ConvGeom g = cm_geom(geom);
+  ConvGeom g = conv_geom_from(geom);
   const int K = g.KH * g.KW * g.CO;
   const int KS = fused ? cm_ks((K + 31) / 32) : cm_ks5((K + 31) / 32);
   const long M = (long)g.B * g.H * g.W;
@@ -1374,9 +1372,8 @@ static int dgrad_mfma_impl(const void* dy, const void* w, const int* geom, void*
   long blocks = (ngroups + CM_WAVES * un - 1) / (CM_WAVES * un);
   if (blocks > 1024) blocks = 1024;
   if (colsum && blocks > 512) blocks = 512;  // one colsum atomic per channel per workgroup
-  const size_t shm = (size_t)(g.C * cm_rs(KS * 4) * 8 + CM_WAVES * 16 * g.C) * sizeof(bf16_raw) +
-                     (size_t)CM_RSLOTS * g.C * (1 + K0 + (bnacc ? 1 : 0)) * sizeof(float) + (size_t)KS * 4 * 16;
-  if (shm > 160u * 1024u) return -2;  // gfx950 LDS per workgroup (C = 128 at K = 512 with the BN sums: 161 KB)
+  const size_t shm = dgrad_mfma_lds(g, KS, K0, bnacc != nullptr);
+  if (shm > kDgradMfmaLdsMax) return -2;
   const int wvec = (uintptr_t)w % 16 == 0;
   static const int dbg = getenv("HOPSX_PHASE_DBG") ? 1 : 0;
   const DgradArgs DA{(const bf16_raw*)dy, (const bf16_raw*)w, (bf16_raw*)dx, (const bf16_raw*)yprev, act_prev, colsum,
@@ -1431,7 +1428,7 @@ bool hopsx_conv_wgrad_mfma_ok(const int* geom) {
 
 extern "C" int hopsx_conv2d_wgrad_mfma(const void* dy, const void* x, const int* geom, float* dw, float* dbias,
                                        const void* y, int yact, hipStream_t st) {
-  ConvGeom g = cm_geom(geom);
+  ConvGeom g = conv_geom_from(geom);
   const int K = g.KH * g.KW * g.C;
   const long M = (long)g.B * g.OH * g.OW;
   const long nchunks = (M + WG_PX - 1) / WG_PX;
@@ -1496,7 +1493,7 @@ static int conv_bwd_pair_gemm(const void* dy, const void* w, const int* geom, vo
                               int act_prev, float* colsum, const void* y, int yact, const void* x, float* dw,
                               float* dbias, const void* addend, hipStream_t st, const BnPre& bp = BnPre{}) {
   if (hopsx_disabled("bwd_pair_gemm")) return -2;
-  ConvGeom g = cm_geom(geom);
+  ConvGeom g = conv_geom_from(geom);
   if (g.C % 8 != 0 || g.CO % 8 != 0 || ((uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)w) % 16 != 0)
     return -2;
   const int M = g.B * g.H * g.W, N = g.C, K = g.KH * g.KW * g.CO;
@@ -1626,8 +1623,8 @@ static int conv2d_bwd_pair_impl(const void* dy, const void* w, const int* geom, 
   }
   if (fused && (!hopsx_conv_dgrad_fused_wgrad_ok(geom, geom0) || !yprev || !colsum || !dw0 || !x0)) return -4;
   if (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)yprev) % 16 != 0) return -2;
-  ConvGeom g = cm_geom(geom);
-  ConvGeom g0 = fused ? cm_geom(geom0) : ConvGeom{};
+  ConvGeom g = conv_geom_from(geom);
+  ConvGeom g0 = fused ? conv_geom_from(geom0) : ConvGeom{};
   const int K0 = fused ? geom0[7] * geom0[8] : 0;
   // ---- dgrad part
   const int Kd = g.KH * g.KW * g.CO;
@@ -1700,11 +1697,7 @@ extern "C" int hopsx_conv2d_fwd_pool(const void* x, const void* w, const int* ge
                                      const float* bias, int act, float p, const unsigned long long* rng, unsigned salt,
                                      int pk, hipStream_t st) {
   if (!hopsx_conv_fwd_pool_ok(geom, act, pk)) return -2;
-  ConvGeom g;
-  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
-  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
-  g.dh = geom[13]; g.dw = geom[14];
-  g.init_div();
+  const ConvGeom g = conv_geom_from(geom);
   const int K = g.KH * g.KW * g.C;
   const int KS = cm_ks((K + 31) / 32);
   const long rows = (long)g.B * (g.OH / pk) * (g.OW / pk) * pk * pk;
@@ -1768,7 +1761,7 @@ extern "C" int hopsx_conv2d_fwd_pool_in(const void* x0, float xscale, float xshi
                                         const unsigned long long* rng, unsigned salt, hipStream_t st) {
   if (!hopsx_conv_fwd_pool_in_ok(geom0, geom, act)) return -2;
   if (((uintptr_t)w | (uintptr_t)out | (uintptr_t)y1) % 16 != 0 || xscale == 0.f) return -3;
-  ConvGeom g = cm_geom(geom);
+  ConvGeom g = conv_geom_from(geom);
   const int K = g.KH * g.KW * g.C;
   const int KS = cm_ks((K + 31) / 32);
   const long rows = (long)g.B * (g.OH / 2) * (g.OW / 2) * 4;

@@ -114,6 +114,16 @@ struct ConvGeom {
   }
 };
 
+// the launchers' 15-entry geometry vector (kernels.conv_geom) -> ConvGeom
+inline ConvGeom conv_geom_from(const int* geom) {
+  ConvGeom g;
+  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3]; g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
+  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
+  g.dh = geom[13]; g.dw = geom[14];
+  g.init_div();
+  return g;
+}
+
 // im2col view of X: (outer = output pixel m, inner = k = (kh, kw, ci))
 struct Im2colLoader {
   const bf16_raw* x;

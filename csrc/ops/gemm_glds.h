@@ -798,10 +798,12 @@ inline bool gg_plan(long M, long N, long K, bool allow_split, GgPlan& p, long mi
   return wgs >= min_wg && wgs < (1L << 31);
 }
 
+// deterministic mode keeps gemm_core.h's engine (one K slice per tile, turn-ordered column sums)
+inline bool gg_on() { return !hopsx_disabled("gg") && !hopsx_deterministic(); }
+
 // launch_gg's own decision, without launching: whether the engine takes the shape, and its plan
 inline bool gg_takes(int M, int N, int K, bool allow_split, GgPlan& p, long min_wg_override = -1) {
-  // deterministic mode keeps gemm_core.h's engine (one K slice per tile, turn-ordered column sums)
-  if (M <= 0 || N <= 0 || K <= 0 || hopsx_disabled("gg") || hopsx_deterministic()) return false;
+  if (M <= 0 || N <= 0 || K <= 0 || !gg_on()) return false;
   static const bool narrow = !hopsx_disabled("gg_n64");
   return gg_plan(M, N, K, allow_split, p, min_wg_override, 256, narrow);
 }

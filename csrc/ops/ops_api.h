@@ -6,6 +6,12 @@
 #include <hip/hip_runtime.h>
 
 enum GemmEpi : int { EPI_STORE_BF16 = 0, EPI_STORE_F32 = 1, EPI_ATOMIC_F32 = 2, EPI_DACT_BF16 = 3 };
+// The engine a conv launcher runs (conv.hip conv_fwd_route / conv_dgrad_route; kernels.CONV_ROUTES, same order): the
+// direct input-layer kernel, the direct MFMA kernel, the gg engine, gemm_core.h's engine with split-K and the ticket
+// finish, that engine unsplit; dgrad's gg forms: parity-class GEMMs, 1x1 strided scatter, dense 1x1, gather.
+enum ConvRoute : int {
+  CONV_DIRECT = 0, CONV_MFMA, CONV_GG, CONV_SPLITK, CONV_GEMM, CONV_GG_PAR, CONV_GG_SCATTER, CONV_GG_DENSE, CONV_GG_GATHER
+};
 
 extern "C" {
 // ---- GEMM / conv (gemm.hip, conv.hip) ----
@@ -174,16 +180,24 @@ int hopsx_conv2d_fwd_mfma(const void* x, const void* w, const int* geom, void* o
 int hopsx_conv2d_fwd_mfma_ex(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
                              float* bnacc, hipStream_t st);
 // Frozen-inference forward: out = act(conv(x, w) + bias[co] + residual[m, co]) (bf16 out; act none or relu), the
-// residual a bf16 tensor of out's layout added before the activation.  hopsx_conv2d_fwd's routing, minus the
-// direct input-layer kernel (which never sees a residual); residual == null IS hopsx_conv2d_fwd (bf16 store).
+// residual a bf16 tensor of out's layout added before the activation.  Routed by conv_fwd_route (conv.hip)
+// as kind 3; residual == null IS hopsx_conv2d_fwd (bf16 store).
 // Nothing is launched and an error returned for: an activation other than none / relu (-2), a residual that is
-// not 16-B aligned (-4) or that overlaps out (-5).
+// not 16-B aligned (-4) or that overlaps out (-5).  Every conv launcher (hopsx_conv2d_fwd, _fwd_res, _fwd_bnstats,
+// _dgrad, _dgrad_bn) returns -6 if the gg engine refused a launch its route had asked gg_takes for (launch_gg and
+// gg_takes make the same test, gemm_glds.h: not reachable today; the launchers no longer fall through to a GEMM).
 int hopsx_conv2d_fwd_res(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
                          const void* residual, hipStream_t st);
-// the route hopsx_conv2d_fwd_res takes for this geometry with 16-B aligned operands (the launcher's own
-// decision): 0 direct MFMA kernel (conv_mfma.hip), 1 the gg engine (gemm_glds.h), 2 gemm_core.h's engine,
-// 3 gemm_core.h's engine with split-K and the in-launch ticket finish
-int hopsx_conv2d_fwd_res_path(const int* geom);
+// The ConvRoute, or the refusal code, a conv launcher takes for this geometry with 16-B aligned operands: the
+// launchers' own decision functions (conv_fwd_route, conv_dgrad_route), nothing launched, no runtime call.
+// kind: 0 hopsx_conv2d_fwd bf16 store, 1 with column sums, 2 fp32 store, 3 hopsx_conv2d_fwd_res with a
+// residual, 4 hopsx_conv2d_fwd_bnstats.  flags: 1 a mask y on dY, 2 an addend, 4 hopsx_conv2d_dgrad_bn, 8 a
+// bias gradient (colsum).  The route names the engine that computes dX: with the gg engine off (HOPSX_DISABLE=gg,
+// deterministic mode) hopsx_conv2d_dgrad also launches dgrad_par_fill_k ahead of the GEMM it reports, for a
+// strided shape whose parity plan passes with classes to fill.
+int hopsx_conv2d_fwd_path(const int* geom, int kind);
+int hopsx_conv2d_dgrad_path(const int* geom, int flags);
+bool hopsx_conv_dgrad_mfma_bn_ok(const int* geom);
 int hopsx_conv2d_fwd_mfma_res(const void* x, const void* w, const int* geom, void* out, const float* bias, int act,
                               const void* res, hipStream_t st);
 // conv forward (bf16 out, no bias / act) whose epilogue also accumulates the BatchNorm statistics
@@ -216,8 +230,8 @@ int hopsx_conv2d_bwd_pair(const void* dy, const void* w, const int* geom, void* 
                           float* colsum, const void* y, int yact, const int* geom0, const void* x0, float xscale,
                           float xshift, float* dw0, const void* x, float* dw, float* dbias, const void* addend,
                           const void* bnz, const float* bnmean, const float* bnrstd, float* bnacc, hipStream_t st);
-// dgrad with the input BN's backward column sums in the epilogue (conv.hip; -2: shape not covered, nothing
-// launched); the _mfma_bn variant is the direct MFMA kernel alone
+// dgrad with the input BN's backward column sums in the epilogue (conv.hip; routed by conv_dgrad_route as a bn
+// caller; -2: shape not covered, nothing launched); the _mfma_bn variant is the direct MFMA kernel alone
 int hopsx_conv2d_dgrad_bn(const void* dy, const void* w, const int* geom, void* dx, const void* yprev, int act_prev,
                           const void* addend, const void* bnz, const float* bnmean, const float* bnrstd, float* bnacc,
                           hipStream_t st);

@@ -26,12 +26,7 @@ extern "C" int hopsx_conv_wgrad_glds_ok(const int* geom) {
 extern "C" int hopsx_conv2d_wgrad_glds(const void* dy, const void* x, const int* geom, float* dw, int force,
                                        hipStream_t st) {
   if (!hopsx_conv_wgrad_glds_ok(geom) || ((uintptr_t)dy | (uintptr_t)x) % 16) return -2;
-  ConvGeom g;
-  g.B = geom[0]; g.H = geom[1]; g.W = geom[2]; g.C = geom[3];
-  g.OH = geom[4]; g.OW = geom[5]; g.CO = geom[6];
-  g.KH = geom[7]; g.KW = geom[8]; g.sh = geom[9]; g.sw = geom[10]; g.ph = geom[11]; g.pw = geom[12];
-  g.dh = geom[13]; g.dw = geom[14];
-  g.init_div();
+  const ConvGeom g = conv_geom_from(geom);
   const int CO = g.CO, N = g.KH * g.KW * g.C, K = g.B * g.OH * g.OW;
   const GgDense dsrc{(const bf16_raw*)dy, (long)CO, K, CO};
   const long mw = force ? 1 : -1;

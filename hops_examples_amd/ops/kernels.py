@@ -201,7 +201,38 @@ def conv2d_fwd(x, w, geom, bias=None, act=0, out=None, colsum=None, in_affine=No
     return out
 
 
-_RES_ROUTES = ("mfma", "gg", "gemm", "splitk")
+# csrc/ops/ops_api.h ConvRoute, in its order
+CONV_ROUTES = ("direct", "mfma", "gg", "splitk", "gemm", "gg_par", "gg_scatter", "gg_dense", "gg_gather")
+_FWD_KINDS = ("store", "colsum", "f32", "res", "bnstats")
+
+
+def _route(code: int):
+    """A launcher's route by name; a refusal stays the launcher's negative return code."""
+    return CONV_ROUTES[code] if code >= 0 else code
+
+
+def _geom15(geom, who):
+    geom = [int(v) for v in geom]
+    if len(geom) != 15:
+        raise ValueError(f"{who}: geom is the 15-entry vector of conv_geom")
+    return geom
+
+
+def conv2d_fwd_path(geom, kind="store"):
+    """The route a forward launcher takes for this geometry with 16-B aligned operands (the launchers' own
+    decision, csrc/ops/conv.hip conv_fwd_route; nothing is launched).  ``kind``: 'store' conv2d_fwd, 'colsum'
+    with column sums, 'f32' with an fp32 ``out``, 'res' conv2d_fwd_res with a residual, 'bnstats'
+    conv2d_fwd_bnstats.  A name from CONV_ROUTES, or the launcher's negative refusal code."""
+    return _route(_C.ext().conv2d_fwd_path(_geom15(geom, "conv2d_fwd_path"), _FWD_KINDS.index(kind)))
+
+
+def conv2d_dgrad_path(geom, y=False, addend=False, bn=False, colsum=False):
+    """The route conv2d_dgrad (``bn``: conv2d_dgrad_bn) takes for this geometry with 16-B aligned operands
+    (csrc/ops/conv.hip conv_dgrad_route; nothing is launched), given which optional operands it gets.  It names the
+    engine that computes dX: with the gg engine off (HOPSX_DISABLE=gg, deterministic mode) conv2d_dgrad also launches
+    the parity fill kernel ahead of the 'gemm' / 'splitk' it reports, for a strided shape whose parity plan passes."""
+    flags = (1 if y else 0) | (2 if addend else 0) | (4 if bn else 0) | (8 if colsum else 0)
+    return _route(_C.ext().conv2d_dgrad_path(_geom15(geom, "conv2d_dgrad_path"), flags))
 
 
 def conv2d_fwd_res(x, w, geom, bias=None, act=0, residual=None, out=None):
@@ -235,13 +266,9 @@ def conv2d_fwd_res(x, w, geom, bias=None, act=0, residual=None, out=None):
 
 
 def conv2d_fwd_res_path(geom) -> str:
-    """The route conv2d_fwd_res takes for this geometry (the launcher's own decision, csrc/ops/conv.hip
-    hopsx_conv2d_fwd_res_path): 'mfma' the direct MFMA kernel, 'gg' the LDS-DMA tile engine, 'gemm' the
-    register-staged engine, 'splitk' that engine with split-K and the in-launch finish."""
-    geom = [int(v) for v in geom]
-    if len(geom) != 15:
-        raise ValueError("conv2d_fwd_res_path: geom is the 15-entry vector of conv_geom")
-    return _RES_ROUTES[_C.ext().conv2d_fwd_res_path(geom)]
+    """The route conv2d_fwd_res takes for this geometry: 'mfma' the direct MFMA kernel, 'gg' the LDS-DMA tile
+    engine, 'gemm' the register-staged engine, 'splitk' that engine with split-K and the in-launch finish."""
+    return conv2d_fwd_path(geom, "res")
 
 
 def conv_fwd_pool_ok(geom, act, pk: int = 2) -> bool:
