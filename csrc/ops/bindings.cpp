@@ -48,7 +48,7 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 // The declarations, set_deterministic, det_lost and dbg_read below are generated from it.
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
-#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval) X(topk)
+#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval) X(topk) X(colsort)
 #define X(tag)                              \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
@@ -490,6 +490,22 @@ HX_PYMOD(HOPSX_MODNAME) {
   });
   m.def("column_stats64", [](u x, int rows, int cols, u out, u st) {
     return hopsx_column_stats64(P<double>(x), rows, cols, P<double>(out), S(st));
+  });
+  m.def("column_sort64", [](u x, long rows, int cols, u keys, u count, u pass_mask, u ws, long ws_words, long cap_bytes,
+                            int max_wg, u st) {
+    return hopsx_column_sort64(P<double>(x), rows, cols, P<unsigned long long>(keys), P<long long>(count),
+                               P<int>(pass_mask), P<unsigned long long>(ws), ws_words, cap_bytes, max_wg, S(st));
+  });
+  m.def("column_sort_tile", []() { return hopsx_column_sort_tile(); });
+  m.def("column_sort_group_cols", [](long rows, int cols, long cap) { return hopsx_column_sort_group_cols(rows, cols, cap); });
+  m.def("column_sort_ws_words", [](long rows, int cols, long cap) { return hopsx_column_sort_ws_words(rows, cols, cap); });
+  m.def("column_runs64", [](u keys, u count, long rows, int cols, u part, u counts, u entropy, int max_wg, u st) {
+    return hopsx_column_runs64(P<unsigned long long>(keys), P<long long>(count), rows, cols,
+                               P<unsigned long long>(part), P<long long>(counts), P<double>(entropy), max_wg, S(st));
+  });
+  m.def("column_order_values64", [](u keys, long rows, int cols, u idx, int m_, u out, u st) {
+    return hopsx_column_order_values64(P<unsigned long long>(keys), rows, cols, P<long long>(idx), m_, P<double>(out),
+                                       S(st));
   });
   m.def("u8_normalize_chan", [](u x, u y, long pixels, int C, std::vector<float> scale, std::vector<float> shift,
                                 int rev, int cout, u st) {

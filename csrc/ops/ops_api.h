@@ -300,6 +300,26 @@ int hopsx_range_window(const long* ts, const int* seg, const long* seg_off, cons
                        const long* lo, const long* hi, int W, double* sum, int* cnt, hipStream_t st);
 // fp64 column statistics for the validation rules: [cols][7] = count, sum, sumsq, min, max, #>=0, #>0
 int hopsx_column_stats64(const double* x, int rows, int cols, double* out_stats, hipStream_t st);
+// ---- per-column sort of fp64 columns and the order rules' statistics (colsort.hip) ----
+// x fp64 [rows][cols] (NaN = missing, only read) -> keys uint64 [cols][rows], every column ascending (order-preserving
+// keys, every NaN = ~0 at the tail), count int64 [cols] = non-NaN values, pass_mask int32 [column groups] = the digit
+// passes that ran.  ws: at least hopsx_column_sort_ws_words(rows, cols, cap_bytes) 64-bit words; cap_bytes (0: 1 GiB)
+// bounds the workspace, the columns are sorted in groups of hopsx_column_sort_group_cols.  rows < 2^31.  Kernel launches
+// only.  hipErrorInvalidValue, nothing launched: a short or misaligned ws, rows out of range.
+int hopsx_column_sort64(const double* x, long rows, int cols, unsigned long long* keys, long long* count,
+                        int* pass_mask, unsigned long long* ws, long ws_words, long cap_bytes, int max_workgroups,
+                        hipStream_t st);
+int hopsx_column_sort_tile();
+int hopsx_column_sort_group_cols(long rows, int cols, long cap_bytes);
+long hopsx_column_sort_ws_words(long rows, int cols, long cap_bytes);
+// over the first count[c] keys of every sorted column: counts int64 [cols][3] = valid, distinct, unique (runs of
+// length 1), entropy fp64 [cols] = ln(n) - sum(L ln L) / n (0 for n = 0).  part: 3 * cols * ceil(rows / tile) words.
+int hopsx_column_runs64(const unsigned long long* keys, const long long* count, long rows, int cols,
+                        unsigned long long* part, long long* counts, double* entropy, int max_workgroups,
+                        hipStream_t st);
+// out[c][j] = the double behind keys[c][idx[c][j]], idx int64 [cols][m] (an index outside [0, rows) gives NaN)
+int hopsx_column_order_values64(const unsigned long long* keys, long rows, int cols, const long long* idx, int m,
+                                double* out, hipStream_t st);
 // per-channel uint8 NHWC -> bf16 image normalisation (C <= 4, optional channel reversal)
 int hopsx_u8_normalize_chan(const unsigned char* x, void* y, long pixels, int C, const float* scale,
                             const float* shift, int rev, int cout, hipStream_t st);

@@ -202,7 +202,7 @@ _NUMERIC_RULES = ("HAS_MIN", "HAS_MAX", "HAS_MEAN", "HAS_SUM", "HAS_STANDARD_DEV
 def prefill_stats(df: pd.DataFrame, feats, stats_cache: dict, device=None) -> str:
     """Aggregates of every numeric feature in ``feats`` in one pass (GPU fp64 kernel on large frames);
     returns the device used ('gpu' / 'cpu')."""
-    feats = [f for f in dict.fromkeys(feats) if f in df.columns and f not in stats_cache]
+    feats = [f for f in dict.fromkeys(feats) if f in df.columns and "count" not in stats_cache.get(f, {})]
     if not feats:
         return stats_cache.get("_device", "cpu")
     x = np.stack([_num(df[f]) for f in feats], 1) if len(df) else np.zeros((0, len(feats)))
@@ -233,17 +233,106 @@ def prefill_stats(df: pd.DataFrame, feats, stats_cache: dict, device=None) -> st
         cnt, s, sq, mn, mx, nn, npos = (float(v) for v in st[j])
         mean = s / cnt if cnt else math.nan
         std = math.sqrt(max(sq / cnt - mean * mean, 0.0)) if cnt else math.nan
-        stats_cache[f] = {"count": int(cnt), "n": len(df), "min": mn if cnt else math.nan,
-                          "max": mx if cnt else math.nan, "sum": s, "mean": mean, "std": std,
-                          "nonneg": nn / cnt if cnt else 1.0, "pos": npos / cnt if cnt else 1.0}
+        stats_cache.setdefault(f, {}).update({  # (an "order" entry of prefill_order stays)
+            "count": int(cnt), "n": len(df), "min": mn if cnt else math.nan, "max": mx if cnt else math.nan, "sum": s,
+            "mean": mean, "std": std, "nonneg": nn / cnt if cnt else 1.0, "pos": npos / cnt if cnt else 1.0})
     stats_cache["_device"] = dev
     return dev
+
+
+# The rules that read the order or the multiplicity of a feature's values.  On the device route they share one sort
+# of the eligible columns (colsort.hip): distinct / unique counts and the entropy from the runs of the sorted column,
+# the quantile from two order statistics.  Elsewhere _metric runs the pandas lines below.
+_ORDER_RULES = ("HAS_NUMBER_OF_DISTINCT_VALUES", "HAS_APPROX_COUNT_DISTINCT", "HAS_DISTINCTNESS", "HAS_UNIQUENESS",
+                "HAS_UNIQUE_VALUE_RATIO", "HAS_ENTROPY", "HAS_APPROX_QUANTILE")
+# Rows from which validate takes the device route for the order rules: the smallest measured size at which the device
+# route won five of five alternating pairs against the pandas route (tools/colsort_bench.py on one MI355X, validate
+# with the 7 order rules x 8 features, upload included; profiles/r20_colsort.txt):
+#   rows         device      pandas     pairs won
+#   100,000       2.5 ms     77.1 ms    5 of 5
+#   1,000,000    24.4 ms   1451.4 ms    5 of 5
+#   10,000,000  259.7 ms  29608.9 ms    5 of 5
+# Nothing below 100,000 rows has been measured.
+ORDER_GPU_MIN_ROWS = 100_000
+DEFAULT_QUANTILE = 0.5
+
+
+def _rule_quantile(rule: Rule) -> float:
+    return DEFAULT_QUANTILE if rule.legal_values is None else float(rule.legal_values[0])
+
+
+def order_eligible(s: pd.Series) -> bool:
+    """Whether fp64 sort keys reproduce pandas' ``nunique`` / ``value_counts`` / ``nanquantile`` on this column:
+    a numeric dtype that is neither bool nor object (``_num`` would turn strings into NaN), and for integers every
+    |v| <= 2^53 (fp64 merges larger ones)."""
+    dt = s.dtype
+    if not pd.api.types.is_numeric_dtype(dt) or pd.api.types.is_bool_dtype(dt) or dt == object:
+        return False
+    if pd.api.types.is_integer_dtype(dt) and len(s):
+        lo, hi = s.min(), s.max()
+        if not pd.isna(lo) and (int(lo) < -(1 << 53) or int(hi) > (1 << 53)):
+            return False
+    return True
+
+
+def prefill_order(df: pd.DataFrame, feats, quantiles, stats_cache: dict, device=None) -> str:
+    """The order statistics of every eligible feature in ``feats`` from ONE device sort: stores
+    ``stats_cache[feat]["order"] = {count, distinct, unique, entropy, quantile: {q: value}}`` and returns 'gpu'; on the
+    host route ('cpu': a frame below ``ORDER_GPU_MIN_ROWS`` rows, no GPU, no eligible feature) it stores nothing."""
+    feats = [f for f in dict.fromkeys(feats) if f in df.columns and "order" not in stats_cache.get(f, {})
+             and order_eligible(df[f])]
+    use_gpu = False
+    try:
+        import torch
+
+        use_gpu = torch.cuda.is_available() and (
+            (device is not None and torch.device(device).type == "cuda")
+            or (device is None and len(df) >= ORDER_GPU_MIN_ROWS))
+    except Exception:  # pragma: no cover
+        pass
+    if not (use_gpu and feats and len(df)):
+        return "cpu"
+    import torch
+
+    from ..ops import kernels as K
+
+    qs = sorted({float(q) for q in quantiles})
+    x = np.stack([_num(df[f]) for f in feats], 1)
+    xt = torch.from_numpy(np.ascontiguousarray(x)).pin_memory().cuda(non_blocking=True)
+    order = K.column_sort64(xt)
+    counts, entropy = K.column_runs64(order)
+    qv = K.column_quantiles64(order, qs) if qs else np.zeros((len(feats), 0))
+    counts, entropy = counts.cpu().numpy(), entropy.cpu().numpy()
+    for j, f in enumerate(feats):
+        stats_cache.setdefault(f, {})["order"] = {
+            "count": int(counts[j, 0]), "distinct": int(counts[j, 1]), "unique": int(counts[j, 2]),
+            "entropy": float(entropy[j]), "quantile": {q: float(qv[j, i]) for i, q in enumerate(qs)}}
+    return "gpu"
+
+
+def _order_metric(n: str, rule: Rule, o: dict):
+    """An order rule's value from a prefill_order entry (None: not held there); the denominators are _metric's."""
+    if n == "HAS_NUMBER_OF_DISTINCT_VALUES" or n == "HAS_APPROX_COUNT_DISTINCT":
+        return float(o["distinct"])
+    if n == "HAS_DISTINCTNESS":
+        return float(o["distinct"] / max(1, o["count"]))
+    if n == "HAS_UNIQUENESS":
+        return float(o["unique"] / max(1, o["count"]))
+    if n == "HAS_UNIQUE_VALUE_RATIO":
+        return float(o["unique"] / max(1, o["distinct"]))
+    if n == "HAS_ENTROPY":
+        return float(o["entropy"])
+    return o["quantile"].get(_rule_quantile(rule))
 
 
 def _metric(rule: Rule, df: pd.DataFrame, feat: str, stats_cache: dict):
     """The measured value for rule on feature (None for row-wise predicates)."""
     n = rule.name
     s = df[feat] if feat in df.columns else None
+    if n in _ORDER_RULES and s is not None and "order" in stats_cache.get(feat, {}):
+        v = _order_metric(n, rule, stats_cache[feat]["order"])
+        if v is not None:
+            return v
     if n == "HAS_SIZE":
         return float(len(df))
     if s is None:
@@ -251,7 +340,7 @@ def _metric(rule: Rule, df: pd.DataFrame, feat: str, stats_cache: dict):
     if n == "HAS_COMPLETENESS":
         return float(s.notna().sum() / max(1, len(s)))
     if n in _NUMERIC_RULES:
-        if feat not in stats_cache:
+        if "count" not in stats_cache.get(feat, {}):
             prefill_stats(df, [feat], stats_cache)
         st = stats_cache[feat]
         return {"HAS_MIN": st["min"], "HAS_MAX": st["max"], "HAS_MEAN": st["mean"], "HAS_SUM": st["sum"],
@@ -269,8 +358,7 @@ def _metric(rule: Rule, df: pd.DataFrame, feat: str, stats_cache: dict):
     if n == "HAS_ENTROPY":
         return _entropy(s)
     if n == "HAS_APPROX_QUANTILE":
-        q = 0.5 if rule.legal_values is None else float(rule.legal_values[0])
-        return float(np.nanquantile(_num(s), q))
+        return float(np.nanquantile(_num(s), _rule_quantile(rule)))
     if n == "HAS_PATTERN":
         pat = re.compile(rule.pattern or ".*")
         vals = s.dropna().astype(str)
@@ -332,6 +420,10 @@ def validate(df: pd.DataFrame, expectations: list[Expectation], validation_id: i
     # one aggregate pass (GPU fp64 kernel on large frames) over every feature a numeric rule reads
     prefill_stats(df, [f for e in expectations for r in e.rules if r.name in _NUMERIC_RULES for f in e.features],
                   cache)
+    # one device sort (large frames) over every feature an order rule reads
+    order_rules = [(r, e.features) for e in expectations for r in e.rules if r.name in _ORDER_RULES]
+    order_device = prefill_order(df, [f for _, fs in order_rules for f in fs],
+                                 [_rule_quantile(r) for r, _ in order_rules if r.name == "HAS_APPROX_QUANTILE"], cache)
     results = []
     for e in expectations:
         rs = []
@@ -355,4 +447,5 @@ def validate(df: pd.DataFrame, expectations: list[Expectation], validation_id: i
         results.append(ExpectationResult(e, rs))
     v = FeatureGroupValidation(validation_id, int(time.time() * 1000), results, commit_time)
     v.aggregates_device = cache.get("_device", "cpu")
+    v.order_device = order_device
     return v

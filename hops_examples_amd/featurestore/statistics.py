@@ -6,6 +6,9 @@ Numeric columns are reduced on the GPU by the hopsx column-statistics kernels
 (one pass for count/sum/sum^2/min/max, one for histograms, one centred Gram
 matrix for Pearson correlations) when a GPU is present and the frame is large
 enough to amortise the transfer; otherwise numpy computes the same values.
+``approximateNumDistinctValues`` of the numeric columns comes from one device
+sort of an fp64 upload on the same condition (``distinct_counts``; measured
+faster than pandas ``nunique`` from 10^5 to 10^7 rows, profiles/r20_colsort.txt).
 """
 from __future__ import annotations
 
@@ -105,6 +108,31 @@ def column_stats(x: np.ndarray, bins: int = 20, correlations: bool = False, hist
     return out
 
 
+def distinct_counts(df: pd.DataFrame, cols, device: bool | None = None) -> dict:
+    """{column: number of distinct non-missing values} for ``cols``.  On the device route (``device`` True, or None
+    and a frame ``_gpu_ok`` accepts) the columns fp64 sort keys count exactly (``rules.order_eligible``) are uploaded
+    as fp64 — the fp32 statistics matrix would merge values — sorted once and counted from the runs (colsort.hip);
+    every other column takes pandas ``nunique``."""
+    out, dev_cols = {}, []
+    if (device or (device is None and _gpu_ok(len(df)))) and len(df):
+        from .rules import order_eligible
+
+        dev_cols = [c for c in cols if order_eligible(df[c])]
+    if dev_cols:
+        import torch
+
+        from ..ops import kernels as K
+
+        x = df[dev_cols].apply(pd.to_numeric, errors="coerce").to_numpy(np.float64)
+        xt = torch.from_numpy(np.ascontiguousarray(x)).pin_memory().cuda(non_blocking=True)
+        counts = K.column_runs64(K.column_sort64(xt))[0].cpu().numpy()
+        out.update({c: int(counts[j, 1]) for j, c in enumerate(dev_cols)})
+    for c in cols:
+        if c not in out:
+            out[c] = int(df[c].nunique(dropna=True))
+    return out
+
+
 def compute(df: pd.DataFrame, cfg: StatisticsConfig | None = None, bins: int = 20) -> dict:
     """hsfs-style statistics JSON: {'columns': [{column, dataType, count, completeness, mean, …}], …}."""
     cfg = cfg or StatisticsConfig()
@@ -113,12 +141,13 @@ def compute(df: pd.DataFrame, cfg: StatisticsConfig | None = None, bins: int = 2
     cols, x = _numeric_matrix(df)
     st = column_stats(x, bins, cfg.correlations, cfg.histograms) if cols else {}
     n = len(df)
+    nd = distinct_counts(df, cols)
     columns = []
     for i, c in enumerate(cols):
         e = {"column": c, "dataType": "Fractional", "count": int(st["count"][i]),
              "completeness": float(st["count"][i] / n) if n else 1.0, "mean": float(st["mean"][i]),
              "stdDev": float(st["stddev"][i]), "minimum": float(st["min"][i]), "maximum": float(st["max"][i]),
-             "sum": float(st["sum"][i]), "approximateNumDistinctValues": int(df[c].nunique(dropna=True))}
+             "sum": float(st["sum"][i]), "approximateNumDistinctValues": nd[c]}
         if cfg.histograms and "hist" in st:
             lo, hi = float(st["min"][i]), float(st["max"][i])
             edges = np.linspace(lo, hi if hi > lo else lo + 1, bins + 1)

@@ -1434,6 +1434,143 @@ def softmax_topk_reference(logits, k: int, dtype=torch.float64):
     return ids.to(torch.int32), scores
 
 
+def _as_f64_2d(x):
+    import numpy as np
+
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.ndim != 2 or a.dtype != np.float64:
+        raise ValueError(f"fp64 [rows, cols] expected, got {a.dtype} {a.shape}")
+    return a
+
+
+def column_key_reference(x):
+    """The sort keys of colsort.hip on the host, uint64 of the shape of the fp64 array ``x``: -0.0 is folded onto
+    +0.0, then with k the bits of the value the key is ``~k`` for a set sign and ``k | 1 << 63`` otherwise, so keys
+    order as the doubles do; every NaN, of any sign or payload, is ``~0``, above the key of +inf
+    (0xFFF0000000000000)."""
+    import numpy as np
+
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    k = a.view(np.uint64).copy()
+    k[k == np.uint64(1 << 63)] = 0
+    neg = (k >> np.uint64(63)).astype(bool)
+    k = np.where(neg, ~k, k | np.uint64(1 << 63))
+    k[np.isnan(a)] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    return k
+
+
+def column_key_decode(keys):
+    """The inverse of ``column_key_reference`` (fp64 numpy array): the all-ones key gives the quiet NaN
+    0x7FF8000000000000.  ``keys``: uint64, or int64 holding the same bits (``ColumnOrder.keys``)."""
+    import numpy as np
+
+    k = keys.detach().cpu().numpy() if isinstance(keys, torch.Tensor) else np.asarray(keys)
+    k = np.ascontiguousarray(k).view(np.uint64)
+    pos = (k >> np.uint64(63)).astype(bool)
+    b = np.where(pos, k & np.uint64(0x7FFFFFFFFFFFFFFF), ~k)
+    b[k == np.uint64(0xFFFFFFFFFFFFFFFF)] = np.uint64(0x7FF8000000000000)
+    return b.view(np.float64)
+
+
+def column_sort_reference(x):
+    """What ``column_key_decode(column_sort64(x).keys)`` must equal bit for bit: fp64 [cols, rows], every column of
+    ``x`` [rows, cols] ascending, -0.0 as +0.0, the NaNs (as the quiet NaN) last."""
+    import numpy as np
+
+    return column_key_decode(np.sort(column_key_reference(_as_f64_2d(x)).T, axis=1))
+
+
+def column_runs_reference(x):
+    """(counts int64 [cols, 3] = valid, distinct, unique; entropy fp64 [cols]) of ``x`` [rows, cols], NaN = missing:
+    the multiplicities are ``np.unique`` on the valid values (-0.0 as +0.0), the entropy is -sum p ln p with
+    ``math.fsum``, 0.0 for an empty column."""
+    import math
+
+    import numpy as np
+
+    a = _as_f64_2d(x)
+    counts = np.zeros((a.shape[1], 3), np.int64)
+    ent = np.zeros(a.shape[1], np.float64)
+    for c in range(a.shape[1]):
+        v = a[:, c]
+        v = v[~np.isnan(v)] + 0.0  # -0.0 + 0.0 = +0.0
+        _, mult = np.unique(v, return_counts=True)
+        n = int(v.size)
+        counts[c] = (n, mult.size, int((mult == 1).sum()))
+        if n:
+            p = mult.astype(np.float64) / n
+            ent[c] = -math.fsum((p * np.log(p)).tolist())
+    return counts, ent
+
+
+def column_quantile_reference(x, qs):
+    """fp64 [cols, len(qs)]: ``np.nanquantile`` of every column of ``x`` [rows, cols] (NaN for an empty column)."""
+    import warnings
+
+    import numpy as np
+
+    a = _as_f64_2d(x)
+    qs = np.atleast_1d(np.asarray(qs, np.float64))
+    out = np.full((a.shape[1], qs.size), np.nan)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for c in range(a.shape[1]):
+            if a.shape[0] and not np.isnan(a[:, c]).all():
+                out[c] = np.nanquantile(a[:, c], qs)
+    return out
+
+
+COLUMN_ORDER_FAMILIES = ("bits", "digits", "equal", "increasing", "decreasing", "allnan", "onenan", "zeros", "ulps",
+                         "tworuns")
+# the families without NaN and infinities: the ones quantiles are compared on
+COLUMN_ORDER_FINITE = ("digits", "equal", "increasing", "decreasing", "zeros", "ulps", "tworuns")
+
+
+def column_order_family(name: str, rows: int, cols: int, seed: int = 0, tile: int = 2048):
+    """fp64 numpy [rows, cols] of one input family of the column-sort tests (every column its own draw):
+    ``bits`` random 64-bit patterns read as doubles (both signs, denormals, infinities, NaNs of every payload),
+    ``digits`` the doubles 0..9, ``equal`` one value, ``increasing`` / ``decreasing`` strictly monotone, ``allnan``,
+    ``onenan`` distinct values and exactly one NaN, ``zeros`` a mix of -0.0 and +0.0 (and 1.0), ``ulps`` 1.0 + k ulp
+    with k < 256 (only the lowest digit differs), ``tworuns`` one value on the first ``tile + 3`` rows, another behind
+    (a run that crosses a tile boundary; fewer rows: the first value only)."""
+    import numpy as np
+
+    rng = np.random.default_rng(1000 * COLUMN_ORDER_FAMILIES.index(name) + seed)
+    x = np.empty((rows, cols), np.float64)
+    for c in range(cols):
+        if name == "bits":
+            b = rng.integers(0, 1 << 64, rows, dtype=np.uint64)
+            special = np.array([0x7FF0000000000000, 0xFFF0000000000000, 0x7FF8000000000001, 0xFFFFFFFFFFFFFFFF,
+                                0x8000000000000000, 0, 1, 0x800FFFFFFFFFFFFF, 0x7FF0000000000001], np.uint64)
+            at = rng.integers(0, rows, min(rows, 2 * special.size))
+            b[at] = special[rng.integers(0, special.size, at.size)]
+            v = b.view(np.float64)
+        elif name == "digits":
+            v = rng.integers(0, 10, rows).astype(np.float64)
+        elif name == "equal":
+            v = np.full(rows, -3.25 + c)
+        elif name == "increasing":
+            v = np.arange(rows, dtype=np.float64) * 0.5 - rows / 3.0 + c
+        elif name == "decreasing":
+            v = -(np.arange(rows, dtype=np.float64) * 0.5 - rows / 3.0 + c)
+        elif name == "allnan":
+            v = np.full(rows, np.nan)
+        elif name == "onenan":
+            v = rng.permutation(rows).astype(np.float64) - rows // 2
+            v[int(rng.integers(0, rows))] = np.nan
+        elif name == "zeros":
+            v = np.array([-0.0, 0.0, 1.0])[rng.integers(0, 3, rows)]
+        elif name == "ulps":
+            v = (np.float64(1.0).view(np.uint64) + rng.integers(0, 256, rows).astype(np.uint64)).view(np.float64)
+        elif name == "tworuns":
+            v = np.where(np.arange(rows) < tile + 3, 7.0 + c, -2.0)
+        else:
+            raise ValueError(f"unknown family {name!r}")
+        x[:, c] = v
+    return x
+
+
 def _act_name(act):
     return {0: None, "none": None, 1: "relu", 2: "sigmoid", 3: "tanh"}.get(act, act)
 

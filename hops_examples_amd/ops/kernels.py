@@ -963,6 +963,135 @@ def column_stats64(x):
     return out
 
 
+class ColumnOrder:
+    """The sorted columns of ``column_sort64``: ``keys`` int64 [cols, rows] holding the uint64 sort keys of every
+    column in ascending (unsigned) order, ``count`` int64 [cols] the non-NaN values per column (the NaN keys are the
+    tail), ``passes`` the digit passes that ran, one list per column group (reading it waits for the sort)."""
+
+    def __init__(self, keys, count, pass_mask, rows, cols, max_workgroups):
+        self.keys, self.count, self.pass_mask = keys, count, pass_mask
+        self.rows, self.cols, self.max_workgroups = rows, cols, max_workgroups
+
+    @property
+    def passes(self):
+        return [[p for p in range(8) if (m >> p) & 1] for m in self.pass_mask.cpu().tolist()]
+
+
+def column_sort_tile() -> int:
+    """Keys per workgroup tile of the column sort (csrc/ops/colsort.hip)."""
+    return int(_C.ext().column_sort_tile())
+
+
+def _sort_dims(rows, cols, ws_cap_bytes, what):
+    rows, cols, cap = int(rows), int(cols), int(ws_cap_bytes)
+    if rows < 0 or cols < 0 or cap < 0:
+        raise ValueError(f"{what}: rows, cols and ws_cap_bytes >= 0 expected")
+    if rows > 0x7FFFFFFF or cols > 0x7FFFFFFF:
+        raise ValueError(f"{what}: rows < 2^31 expected, got {rows}")
+    return rows, cols, cap
+
+
+def column_sort_ws_words(rows, cols, ws_cap_bytes=0) -> int:
+    """int64 words of workspace ``column_sort64`` needs for fp64 [rows, cols]: one copy of a column group's keys plus
+    its digit histograms, the group sized so that this stays under ``ws_cap_bytes`` (0: 1 GiB; one column always
+    goes)."""
+    rows, cols, cap = _sort_dims(rows, cols, ws_cap_bytes, "column_sort_ws_words")
+    return int(_C.ext().column_sort_ws_words(rows, cols, cap))
+
+
+def column_sort64(x, max_workgroups=0, ws=None, ws_cap_bytes=0):
+    """Every column of ``x`` (fp64 [rows, cols] on the GPU, NaN = missing, not written) sorted: a ``ColumnOrder``
+    (csrc/ops/colsort.hip: an LSD radix sort of order-preserving 64-bit keys).  ``ws``: an optional caller-owned int64
+    workspace of at least ``column_sort_ws_words(rows, cols, ws_cap_bytes)`` words; ``max_workgroups`` caps the grids
+    (0: default).  The result does not depend on either, nor on the column grouping ``ws_cap_bytes`` causes.  Every
+    refusal is a ValueError raised before any launch."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("column_sort64: x [rows, cols] expected")
+    if x.dtype != torch.float64:
+        raise ValueError(f"column_sort64: fp64 expected, got {x.dtype}")
+    if not x.is_cuda:
+        raise ValueError("column_sort64: expected a GPU tensor")
+    if not x.is_contiguous():
+        raise ValueError("column_sort64: expected a contiguous tensor")
+    rows, cols, cap = _sort_dims(x.shape[0], x.shape[1], ws_cap_bytes, "column_sort64")
+    if int(max_workgroups) < 0:
+        raise ValueError("column_sort64: max_workgroups >= 0 expected")
+    need = column_sort_ws_words(rows, cols, cap)
+    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.int64 or not ws.is_cuda
+                           or ws.device != x.device or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"column_sort64: ws must be a contiguous int64 tensor of at least {need} words on {x.device}")
+    ext = _C.ext()
+    gcols = int(ext.column_sort_group_cols(rows, cols, cap)) if rows and cols else 0
+    keys = torch.empty(cols, rows, device=x.device, dtype=torch.int64)
+    count = torch.zeros(cols, device=x.device, dtype=torch.int64)
+    pass_mask = torch.zeros((cols + gcols - 1) // gcols if gcols else 0, device=x.device, dtype=torch.int32)
+    if rows and cols:
+        if ws is None:
+            ws = torch.empty(need, device=x.device, dtype=torch.int64)
+        check(ext.column_sort64(ptr(x), rows, cols, ptr(keys), ptr(count), ptr(pass_mask), ptr(ws), ws.numel(), cap,
+                                int(max_workgroups), stream()), "column_sort64")
+    return ColumnOrder(keys, count, pass_mask, rows, cols, int(max_workgroups))
+
+
+def column_runs64(order):
+    """(counts int64 [cols, 3] = valid, distinct, unique; entropy fp64 [cols]) of the sorted columns: ``unique`` counts
+    the values that occur once, the entropy is that of the value frequencies (natural log; 0.0 for an empty column).
+    Integer counts and a fixed-order fp64 sum: the same bits for any grid and any column grouping of the sort."""
+    keys = order.keys
+    cols, rows = keys.shape
+    counts = torch.zeros(cols, 3, device=keys.device, dtype=torch.int64)
+    entropy = torch.zeros(cols, device=keys.device, dtype=torch.float64)
+    if rows and cols:
+        tiles = (rows + column_sort_tile() - 1) // column_sort_tile()
+        part = torch.empty(3 * cols * tiles, device=keys.device, dtype=torch.int64)
+        check(_C.ext().column_runs64(ptr(keys), ptr(order.count), rows, cols, ptr(part), ptr(counts), ptr(entropy),
+                                     order.max_workgroups, stream()), "column_runs64")
+    return counts, entropy
+
+
+def column_order_values64(order, idx):
+    """fp64 [cols, m]: the values at the positions ``idx`` (int64 [cols, m], each in [0, rows)) of the sorted columns
+    (position count[c] - 1 is the largest non-NaN value; -0.0 comes back as +0.0)."""
+    keys = order.keys
+    cols, rows = keys.shape
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != cols \
+            or not idx.is_cuda or idx.device != keys.device or not idx.is_contiguous():
+        raise ValueError(f"column_order_values64: idx must be a contiguous int64 [{cols}, m] tensor on {keys.device}")
+    m = idx.shape[1]
+    out = torch.full((cols, m), float("nan"), device=keys.device, dtype=torch.float64)
+    if rows and cols and m:
+        check(_C.ext().column_order_values64(ptr(keys), rows, cols, ptr(idx), m, ptr(out), stream()),
+              "column_order_values64")
+    return out
+
+
+def column_quantiles64(order, qs):
+    """numpy fp64 [cols, len(qs)]: the ``np.nanquantile`` (linear) of every column, bit for bit.  Per column and q the
+    two order statistics around q * (count - 1) come from one ``column_order_values64`` call; the interpolation between
+    them is numpy's own, on the host.  NaN for an empty column."""
+    import numpy as np
+
+    qs = np.atleast_1d(np.asarray(qs, np.float64))
+    if qs.ndim != 1 or not ((qs >= 0) & (qs <= 1)).all():
+        raise ValueError("column_quantiles64: quantiles in [0, 1] expected")
+    cols = order.keys.shape[0]
+    out = np.full((cols, qs.size), np.nan)
+    if not cols or not qs.size or not order.keys.shape[1]:
+        return out
+    n = order.count.cpu().numpy()
+    vi = qs[None, :] * (np.maximum(n, 1)[:, None] - 1)
+    lo = np.floor(vi).astype(np.int64)
+    hi = np.minimum(lo + 1, np.maximum(n, 1)[:, None] - 1)
+    g = vi - lo
+    idx = torch.from_numpy(np.ascontiguousarray(np.concatenate([lo, hi], 1))).to(order.keys.device)
+    v = column_order_values64(order, idx).cpu().numpy()
+    for c in range(cols):
+        if n[c]:
+            for j in range(qs.size):
+                out[c, j] = np.quantile(np.array([v[c, j], v[c, qs.size + j]]), g[c, j])
+    return out
+
+
 def column_hist(x, mins, maxs, bins):
     rows, cols = x.shape
     hist = torch.zeros(cols, bins, device=x.device, dtype=torch.int32)
