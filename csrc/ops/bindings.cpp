@@ -22,6 +22,7 @@
 #include "ops_api.h"
 extern "C" int hopsx_mnist_persist_occupancy(int dp);  // mnist_persist.hip
 extern "C" void hopsx_mnist_persist_reload_knobs();     // mnist_persist.hip
+extern "C" int hopsx_mnist_persist_hand();              // mnist_persist.hip: Args::hand of the last launch
 extern "C" int hopsx_pad_cin(const float* w, long R, int C, int cp, float* out, void* out16, hipStream_t st);
 extern "C" int hopsx_unpad_cin_add(float* gpad, long R, int C, int cp, float* tgt, hipStream_t st);  // elementwise.hip
 
@@ -192,6 +193,7 @@ HX_PYMOD(HOPSX_MODNAME) {
   });
   m.def("taxi_eval_bins", []() { return hopsx_taxi_eval_bins(); });
   m.def("mnist_persist_reload_knobs", []() { hopsx_mnist_persist_reload_knobs(); });
+  m.def("mnist_persist_hand", []() { return hopsx_mnist_persist_hand(); });
   m.def("mnist_persist_occupancy", [](int dp) { return hopsx_mnist_persist_occupancy(dp); });
   m.def("wave_sum_probe", [](u x, long rows, u out_ref, u out_tree, u st) {
     return hopsx_wave_sum_probe(P<float>(x), rows, P<float>(out_ref), P<float>(out_tree), S(st));

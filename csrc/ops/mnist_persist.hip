@@ -104,6 +104,21 @@ constexpr int HAND_FMAX_SHIFT = 20;      // 4 bits: chunks that may run inside t
 constexpr int HAND_GATEA_SHIFT = 18;     // 2 bits: the one-line gate in front of the heads' A wait (HOPSX_PERSIST_GATE_A)
 constexpr int HAND_HEAD_REGS = 1 << 24;  // the one-wave head's operands in registers from the top of the step
 constexpr int HAND_HEAD_TREE = 1 << 25;  // its ten logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN bits 1, 2)
+// The positions' local compute staged wave-locally (position_wg; profiles/r21_persist_wave_local.txt,
+// HOPSX_PERSIST_WLOCAL, one bit per part).  Where the thread-to-data maps make the wave that writes an LDS tile the
+// only wave that reads it, the workgroup barrier between the two is a wave-level ordering point (wave_lds_order), and
+// a wave publishes its own block of A and of C's part 1 without waiting for the others.  No float operation, payload
+// byte, flag or epoch changes; 0 is the parent's path
+constexpr int HAND_WL_FWD = 1 << 4;  // XIN fill -> conv1 -> conv2 without workgroup barriers
+constexpr int HAND_WL_A = 1 << 5;    // a wave publishes its own 32 x 32 block of A
+constexpr int HAND_WL_BWD = 1 << 6;  // pool backward -> conv2 wgrad -> C part 1 per wave, ONE barrier before the conv2 dgrad
+// -DHOPSX_PERSIST_WLOCAL_FIXED=n (tools/persist_isa.py only): the parts are n at compile time, so the assembly has
+// one arm of every branch on them and the static instruction table is that of ONE path
+#ifdef HOPSX_PERSIST_WLOCAL_FIXED
+#define HOPSX_WL_HAND(a) (((HOPSX_PERSIST_WLOCAL_FIXED) & 7) << 4)
+#else
+#define HOPSX_WL_HAND(a) ((a).hand)
+#endif
 constexpr int NLINE_A = (NPOS + 31) / 32;  // 128-byte lines of the A flag row
 // the 32 lane-owned fc1 updates of a step in chunks of FCH, in the order of the whole update (ii, j, r).  A chunk has
 // to stay well below a flag round trip (it runs between a poll's loads and the ballot that consumes them): 4 updates
@@ -212,7 +227,8 @@ struct Args {
   // (HOPSX_PERSIST_GATE); bits 16..17: the waits that are filled with work that is ready early
   // (HOPSX_PERSIST_FILL, HAND_FILL_*); bits 20..23: chunks of the fc1 update the owners may run inside the C wait
   // (HOPSX_PERSIST_FILL_MAX); bits 18..19: the gate in front of the heads' A wait (HOPSX_PERSIST_GATE_A); bits 24..25:
-  // the one-wave head's operands in registers, its logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN, HAND_HEAD_*)
+  // the one-wave head's operands in registers, its logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN, HAND_HEAD_*);
+  // bits 4..6: the positions' wave-local staging (HOPSX_PERSIST_WLOCAL, HAND_WL_*)
   int hand;
   int gate_a_tk;  // wall-clock ticks the A gate watches its line before it gives way to the full wait (_GATE_A_US)
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
@@ -385,6 +401,19 @@ __device__ __forceinline__ long conv_idx(const Args& a, int j) {
   if (j < OFF_W1) return a.off[3] + (j - OFF_B2);
   if (j < OFF_B1) return a.off[0] + (j - OFF_W1);
   return a.off[1] + (j - OFF_B1);
+}
+
+// Ordering point between LDS stores and LDS reads of ONE wave (other lanes' data, nothing another wave wrote): the
+// compiler moves no LDS access across it (it sees per-thread addresses that do not alias and would otherwise hoist the
+// reads), and the wave waits until its own LDS operations have completed
+__device__ __forceinline__ void wave_lds_order() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+// `wl` (workgroup-uniform: a bit of Args::hand) chooses the wave-level point over the workgroup barrier it stands for
+__device__ __forceinline__ void wave_or_wg(bool wl) {
+  if (wl) wave_lds_order();
+  else __syncthreads();
 }
 
 __device__ __forceinline__ void stamp(const Args& a, int s, int ph) {
@@ -635,7 +664,11 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     stamp(a, s, 0);
     XIN[xb * 16 + xr * 4 + 2 * xh] = (float)(xv & 0xFFu) * a.xscale + a.xshift;
     XIN[xb * 16 + xr * 4 + 2 * xh + 1] = (float)(xv >> 8) * a.xscale + a.xshift;
-    __syncthreads();
+    // XIN fill -> conv1 is wave-local: xb = tid >> 3 writes images 8w .. 8w + 7, conv1's bg = tid >> 5 reads images
+    // 8w .. 8w + 7.  XIN's cross-wave readers are the conv1 weight gradient (images 16 mh ..), behind the barrier in
+    // front of the fc1 partial product below, and it ends before the barrier behind RED; CW1 / CB1 were written
+    // behind the D load's barrier
+    wave_or_wg(HOPSX_WL_HAND(a) & HAND_WL_FWD);
     // ---- conv1 (VALU): 32 images x 3x3 positions x 32 channels ----
     {
       const int ci = tid & 31, bg = tid >> 5;
@@ -664,7 +697,13 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           }
       }
     }
-    __syncthreads();
+    // conv1 -> conv2 is wave-local: conv1 wrote C1 of images 8w .. 8w + 7, conv2's A fragments read images
+    // b = 4 (2w + ii) + (fr >> 2), the same ones; W2 and CB2 were written behind the D load's barrier, KEEP behind the
+    // B wait's (or the D wait's) barriers.  C1 is read by every wave in the backward (cfrag, c1v) and next written by
+    // the next step's conv1: the barrier behind RED, the one in front of C's part 2, the C-publish barrier and the D
+    // load's barrier lie between.  POOL / AM, written below, are published by the barrier in front of the fc1 partial
+    // product, which stays: its A fragments read every image's POOL row
+    wave_or_wg(HOPSX_WL_HAND(a) & HAND_WL_FWD);
     // ---- conv2 (MFMA, rows (b, q) = b*4 + q, k = tap*32 + ci) + bias + relu + max-pool + dropout ----
     // (one wave per SIMD: an LDS read that is waited for at once exposes its whole latency, so every phase below
     // issues its LDS reads in batches ahead of their uses — the fragments of MFMA step kk + 1 while step kk's MFMAs
@@ -773,15 +812,34 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
 #pragma unroll
           for (int r = 0; r < 4; ++r) STG[(i * 16 + fq * 4 + r) * HID + (2 * w + jj) * 16 + fr] = acc[i][jj][r];
     }
-    __syncthreads();
     {  // publish A
       const auto R = rsrc(a.slabA + ((long)par * NPOS + p) * (B * HID));
       f32x4 v[4];  // every LDS read of the staging tile first, then the write-through stores
+      if (HOPSX_WL_HAND(a) & HAND_WL_A) {
+        // Wave w's accumulators are columns 32w .. 32w + 31 of all 32 rows: one whole 128-byte line per image.  It
+        // reads them back itself — chunk c = lane + 64 k is row c >> 3, 16-byte piece c & 7 of its columns, so each
+        // store instruction writes 8 whole lines — and stores without waiting for the other waves.  STG's first
+        // 16 KB were last read by the previous step's C part 1, many barriers back; they are next written by the
+        // conv2 weight gradient, behind the B wait's barrier, which every wave passes after this read-back
+        wave_lds_order();
+        int off[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 4; ++k) {
+          const int c = lane + 64 * k;
+          off[k] = (c >> 3) * HID + 32 * w + (c & 7) * 4;
+          v[k] = *(const f32x4*)(STG + off[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) bst16<SC1>(R, (tid + 256 * k) * 16, v[k]);
+        for (int k = 0; k < 4; ++k) bst16<SC1>(R, off[k] * 4, v[k]);
+      } else {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = *(const f32x4*)(STG + (tid + 256 * k) * 4);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) bst16<SC1>(R, (tid + 256 * k) * 16, v[k]);
+      }
       drain();
       __syncthreads();
       if (tid == 0) flag_store(a.flags + FL_A + p, ep);
@@ -802,7 +860,8 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     if (s + 1 < a.nsteps) xv = xload(s + 1);  // next step's patch, consumed next iteration
     stamp(a, s, 2);
     // the next step's keep mask, at the head of the B wait: the heads need ~6 us from here, and KEEP was last read
-    // by this step's conv2 epilogue, two barriers back
+    // by this step's conv2 epilogue, two barriers back (draw_keep writes other waves' images: the barrier in front of
+    // the fc1 partial product and the one in the A publish between drain and flag; neither is one HAND_WL_* removes)
     if ((a.hand & HAND_FILL_KEEP) && s + 1 < a.nsteps) draw_keep(s + 1);
     // ---- B: dh of all 32 images ----
     // (step 0: the heads run on this GPU only, so a B that has not come within tmo0 means workgroups of
@@ -863,6 +922,7 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     };
     unsigned fleft = (1u << NFCH) - 1u;
     unsigned char amv[2][4];  // the pool backward's argmax bytes, read with the fragments
+    const bool wlb = HOPSX_WL_HAND(a) & HAND_WL_BWD;
     {
       // every fragment and the 8 argmax bytes in flight before the first MFMA
       // (the weight gradient, which only the Adadelta at the end of the step needs, is computed behind the
@@ -925,8 +985,13 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
         }
       };
       auto afrag = [&](int kk, int st) { af[st] = lds8(DC2 + (w * 16 + fr) * DCS + kk * 32 + fq * 8); };
+      // Pool backward -> this weight gradient is wave-local: the pool backward wrote DC2 rows co = 16w + fr, afrag
+      // reads rows 16w + fr.  DC2 was last read across waves by the previous step's conv2 input gradient, many
+      // barriers back; this step's reads it behind the one workgroup barrier of the backward, below.  C1 is stable
+      // since the forward, STG[OFF_B2 + co] is read behind the barrier in front of C's part 2
+      if (wlb) wave_lds_order();
       cfrag(0, 0);  // (C1 is this step's conv1 output: readable ahead of the barrier that publishes DC2)
-      __syncthreads();
+      if (!wlb) __syncthreads();
       stamp(a, s, 4);
       afrag(0, 0);
 #pragma unroll
@@ -943,30 +1008,55 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
       for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) STG[(w * 16 + fq * 4 + r) * 128 + j * 16 + fr] = acc[j][r];
+      if (wlb) {
+        // publish C, part 1, per wave: its accumulators are STG rows 16w .. 16w + 15, 8 KB contiguous in the slabC
+        // row.  It reads them back itself (chunk lane + 64 k: each store instruction writes 8 whole lines) and stores
+        // as soon as its own MFMAs are done, ahead of the backward's one barrier.  These rows of STG are next
+        // written by the next step's fc1 partial product, many barriers on
+        wave_lds_order();
+        const auto R = rsrc(a.slabC + ((long)par * NPOS + p) * NCONV);
+        constexpr int NK = OFF_B2 / 4 / 256;
+        f32x4 v[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = *(const f32x4*)(STG + (w * (64 * NK) + lane + 64 * k) * 4);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) bst16<SC1>(R, (w * (64 * NK) + lane + 64 * k) * 16, v[k]);
+      }
     }
     // ---- conv2 input gradient -> col2im -> relu' -> conv1 weight / bias gradient ----
     {
       const int mh = w >> 1, h = w & 1, ci = h * 16 + fr;
-      // both k steps' fragments are read ahead of the barrier below (DC2 and W2 are
-      // stable here), so they arrive while the publish's staging reads and stores issue
+      // without HAND_WL_BWD both k steps' fragments are read ahead of the barrier below (DC2 and W2 are
+      // stable there), so they arrive while the publish's staging reads and stores issue
       bf16x8 af[2][4], bfr[2][4];
+      auto dfrag = [&]() {
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int k1 = kk * 32 + 8 * fq + tq;
+        for (int kk = 0; kk < 2; ++kk) {
+          const int k1 = kk * 32 + 8 * fq + tq;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m0 = (mh * 4 + i) * 16 + 4 * tp;
-          af[kk][i] = lds_tr(DC2 + k1 * DCS + m0, DC2 + (k1 + 4) * DCS + m0);
+          for (int i = 0; i < 4; ++i) {
+            const int m0 = (mh * 4 + i) * 16 + 4 * tp;
+            af[kk][i] = lds_tr(DC2 + k1 * DCS + m0, DC2 + (k1 + 4) * DCS + m0);
+          }
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int c0 = (2 * t + h) * 16 + 4 * tp;
+            bfr[kk][t] = lds_tr(W2 + k1 * W2S + c0, W2 + (k1 + 4) * W2S + c0);
+          }
         }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int c0 = (2 * t + h) * 16 + 4 * tp;
-          bfr[kk][t] = lds_tr(W2 + k1 * W2S + c0, W2 + (k1 + 4) * W2S + c0);
-        }
-      }
-      __syncthreads();
-      {  // publish C, part 1: the conv2 weight gradient (8192 floats) now; its write-through stores drain
-         // while the conv2 input gradient and the conv1 gradient below are computed
+      };
+      // The transposed DC2 reads cross waves (every row co, written by wave co >> 4).  Without HAND_WL_BWD the barrier
+      // in front of the weight gradient published DC2 and this one the staging tile; with it this is the backward's
+      // ONE workgroup barrier: DC2 is read behind it, and C's part 1 has left ahead of it
+      // (one copy of the reads, a barrier on either side of it: with the reads in both arms of a branch the compiler
+      // kept both sets of 64 registers and the data-parallel instantiation spilled)
+      if (wlb) __syncthreads();
+      dfrag();
+      if (!wlb) {
+        __syncthreads();
+        // publish C, part 1: the conv2 weight gradient (8192 floats) now; its write-through stores drain
+        // while the conv2 input gradient and the conv1 gradient below are computed
         const auto R = rsrc(a.slabC + ((long)par * NPOS + p) * NCONV);
         constexpr int NK = OFF_B2 / 4 / 256;
         f32x4 v[NK];  // every LDS read of the staging tile first, then the write-through stores
@@ -1761,6 +1851,11 @@ __global__ __launch_bounds__(256, 1) void mnist_persist_k(const Args a) {
 // fv:   drop_p xscale xshift lr gscale wd rho eps
 static int g_persist_reload = 0;
 extern "C" void hopsx_mnist_persist_reload_knobs() { g_persist_reload = 1; }
+// Args::hand of the last launch (0 before the first): what the knobs came to, for the tests that compare settings.
+// One word per process: with several engines or loopback ranks it is whichever launched last (the knobs themselves are
+// per process too, so every launch between two reloads carries the same word)
+static int g_persist_hand = 0;
+extern "C" int hopsx_mnist_persist_hand() { return g_persist_hand; }
 
 extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, int ni, const float* fv, int nf,
                                    hipStream_t st) {
@@ -1806,7 +1901,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
   static int kn_tagged, kn_gate, kn_poll1, kn_prog, kn_fill, kn_fmax;
-  static int kn_gate_a, kn_gate_a_tk, kn_head;
+  static int kn_gate_a, kn_gate_a_tk, kn_head, kn_wlocal;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1871,6 +1966,10 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     const long gus = hopsx_env_int("HOPSX_PERSIST_GATE_A_US", 20);
     kn_gate_a_tk = (int)(gus >= 0 && gus <= 1000000 ? gus * 100 : 2000);  // us -> 100 MHz ticks
     kn_head = (int)(hopsx_env_int("HOPSX_PERSIST_HEAD_CHAIN", 3) & 3);
+    // the positions' wave-local staging (position_wg; profiles/r21_persist_wave_local.txt), one bit per part, default
+    // all: 1 the forward up to the pooled tile without workgroup barriers, 2 A published per wave, 4 the backward
+    // with one barrier and C's part 1 published per wave; 0 is the path of the build before it
+    kn_wlocal = (int)(hopsx_env_int("HOPSX_PERSIST_WLOCAL", 7) & 7);
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1882,7 +1981,9 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.pollw_d = kn_d;
   a.head1w = kn_head1w;
   a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8) | (kn_fill << 16) | (kn_fmax << HAND_FMAX_SHIFT) |
-           (kn_gate_a << HAND_GATEA_SHIFT) | (kn_head & 1 ? HAND_HEAD_REGS : 0) | (kn_head & 2 ? HAND_HEAD_TREE : 0);
+           (kn_gate_a << HAND_GATEA_SHIFT) | (kn_head & 1 ? HAND_HEAD_REGS : 0) | (kn_head & 2 ? HAND_HEAD_TREE : 0) |
+           (kn_wlocal & 1 ? HAND_WL_FWD : 0) | (kn_wlocal & 2 ? HAND_WL_A : 0) | (kn_wlocal & 4 ? HAND_WL_BWD : 0);
+  g_persist_hand = a.hand;
   a.gate_a_tk = kn_gate_a_tk;
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;
   a.inv_gb = 1.f / (float)(world * B);

@@ -152,6 +152,8 @@ int hopsx_taxi_step2(const uint64_t* ptrs, int np, const long* iv, int ni, const
 int hopsx_mnist_persist(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf,
                         hipStream_t st);
 void hopsx_mnist_persist_geom(long* g);
+// Args::hand of the last launch: what the HOPSX_PERSIST_ launch knobs came to (bits 4..6: HOPSX_PERSIST_WLOCAL)
+int hopsx_mnist_persist_hand();
 // probe: wave_sum and wave_sum_tree (common.h) of each 64-value row of x, every lane's result: out_* [rows][64]
 int hopsx_wave_sum_probe(const float* x, long rows, float* out_ref, float* out_tree, hipStream_t st);
 // ---- flagship MNIST CNN: forward-only inference of n resident uint8 images in one launch (mnist_eval.hip) ----

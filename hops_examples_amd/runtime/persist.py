@@ -59,6 +59,15 @@ def geometry() -> dict:
     return _GEOM
 
 
+def launch_knobs() -> dict:
+    """What the environment's launch knobs came to in the LAST launch of this process (the host wrapper reads them
+    once and again after ``mnist_persist_reload_knobs()``): the kernel's hand-off word and the parts of
+    ``HOPSX_PERSIST_WLOCAL`` (the positions' wave-local staging, bits 4..6 of it; 0 before the first launch).  One word per process, like the
+    knobs: with several engines it is whichever launched last."""
+    hand = int(_ext().mnist_persist_hand())
+    return {"hand": hand, "wlocal": (hand >> 4) & 7}
+
+
 class PersistentError(RuntimeError):
     pass
 

@@ -32,12 +32,12 @@ OPS = os.path.join("csrc", "ops")
 DEFAULT = ["mnist_persist.hip", "mnist_eval.hip", "taxi_step.hip", "taxi_eval.hip"]
 
 
-def compile_asm(src, out, resources=False):
+def compile_asm(src, out, resources=False, defines=()):
     """`src` to gfx950 assembly at `out` with the build's flags; returns the compiler's output (the
     resource-usage remarks with `resources`).  The one place the command line is spelled."""
     from hops_examples_amd import _build
 
-    cmd = [_build.HIPCC, *_build.HIP_FLAGS, *_build._py_includes(), f"-I{os.path.dirname(src)}",
+    cmd = [_build.HIPCC, *_build.HIP_FLAGS, *defines, *_build._py_includes(), f"-I{os.path.dirname(src)}",
            "--cuda-device-only", "-S", src, "-o", out]
     if resources:
         cmd.append("-Rpass-analysis=kernel-resource-usage")
