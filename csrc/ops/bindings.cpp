@@ -49,7 +49,7 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 // The declarations, set_deterministic, det_lost and dbg_read below are generated from it.
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
-#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(taxi_eval) X(topk) X(colsort)
+#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(cnn_eval) X(taxi_eval) X(topk) X(colsort)
 #define X(tag)                              \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
@@ -187,6 +187,15 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_mnist_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), S(st));
   });
   m.def("mnist_eval_tile", []() { return hopsx_mnist_eval_tile(); });
+  // the same for the E1 / E8 / E11 CNN family (runtime/cnn_eval.py)
+  m.def("cnn_eval", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, u st) {
+    return hopsx_cnn_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), S(st));
+  });
+  m.def("cnn_eval_plan", [](int k, int p, int pad) {
+    std::vector<int> out(4);
+    if (hopsx_cnn_eval_plan(k, p, pad, out.data()) != 0) out.clear();
+    return out;
+  });
   // one-launch sliced evaluation of the taxi wide & deep model (runtime/taxi_eval.py)
   m.def("taxi_eval", [](std::vector<uint64_t> p, std::vector<long> iv, u st) {
     return hopsx_taxi_eval(p.data(), (int)p.size(), iv.data(), (int)iv.size(), S(st));

@@ -20,11 +20,12 @@
 // Contract: an image's outputs depend only on that image and the weights — the MFMA rows of different
 // images never mix, tail rows of the last tile are computed from zeros, never loaded past xs + N * 784 or
 // ys + N, never stored and never counted.  `totals` = {sum of loss, hits} is deterministic: every tile
-// writes a partial {fixed-tree sum of its 32 losses, hit count} and a second one-workgroup kernel sums the
+// writes a partial {fixed-tree sum of its 32 losses, hit count} and a second one-workgroup kernel (eval_totals.h) sums the
 // partials in an order that depends only on the number of tiles (no float atomics, no dependence on the
 // grid size).  A label outside [0, 10) is reported through hx_guard, selects no logit, and gives loss 0 /
 // hit 0.  The launch path allocates nothing, synchronises nothing and issues no memset: capture-safe.
 #include "common.h"
+#include "eval_totals.h"
 #include "mnist_cnn.h"
 #include "wg_prims.h"
 
@@ -297,34 +298,6 @@ __global__ __launch_bounds__(256, 2) void mnist_eval_k(const Args a) {
   }
 }
 
-// totals = {sum of the tiles' loss partials, hits}: thread k sums tiles k, k + 256, ... in that order, then a
-// fixed LDS tree — an order that depends only on the number of tiles; the hits are summed as integers
-__global__ __launch_bounds__(256) void mnist_eval_totals_k(const float* part, int ntiles, float* totals) {
-  __shared__ float sl[256];
-  __shared__ int sh[256];
-  const int tid = threadIdx.x;
-  float l = 0.f;
-  int h = 0;
-  for (int k = tid; k < ntiles; k += 256) {
-    l += part[2 * k];
-    h += (int)part[2 * k + 1];
-  }
-  sl[tid] = l;
-  sh[tid] = h;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) {
-      sl[tid] += sl[tid + s];
-      sh[tid] += sh[tid + s];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    totals[0] = sl[0];
-    totals[1] = (float)sh[0];
-  }
-}
-
 }  // namespace mnistev
 
 HOPSX_DBG_TU(mnist_eval)
@@ -375,7 +348,7 @@ extern "C" int hopsx_mnist_eval(const uint64_t* p, int np, const long* iv, int n
     if (dev >= 0 && dev < 64) attr[dev] = true;
   }
   hipLaunchKernelGGL(mnist_eval_k, dim3((unsigned)grid), dim3(256), LDS_BYTES, st, a);
-  if (a.ys) hipLaunchKernelGGL(mnist_eval_totals_k, dim3(1), dim3(256), 0, st, a.part, a.ntiles, totals);
+  if (a.ys) hipLaunchKernelGGL(evtot::eval_totals_k, dim3(1), dim3(256), 0, st, a.part, a.ntiles, totals);
   return (int)hipGetLastError();
 }
 

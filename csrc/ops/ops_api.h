@@ -160,6 +160,12 @@ int hopsx_wave_sum_probe(const float* x, long rows, float* out_ref, float* out_t
 // ptrs: master shadow xs ys(0 = logits only) logits loss hit totals part   iv: off[8] n max_workgroups   fv: xscale xshift
 int hopsx_mnist_eval(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, hipStream_t st);
 int hopsx_mnist_eval_tile();
+// ---- E1 / E8 / E11 CNN family (runtime k, pool, padding): the same in one launch (cnn_eval.hip) ----
+// hopsx_mnist_eval's argument layout with iv = off[8] n max_workgroups k p pad(0 valid, 1 same) and, optionally,
+// fv[2..3] = the low float halves of xscale / xshift (conv1 runs in fp64 on hi + lo; absent: lo = 0); plan: out =
+// {images per tile, pooled size s, fc1 in-features, LDS bytes} of the launcher's own decision, -2 outside the family
+int hopsx_cnn_eval(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, hipStream_t st);
+int hopsx_cnn_eval_plan(int k, int p, int pad, int* out);
 // ---- Chicago-taxi wide & deep: forward + sliced metric accumulators of n resident rows in one launch (taxi_eval.hip) ----
 // ptrs: master shadow dense cat label(0 = logits / probabilities only) logit prob loss hit acc
 // iv:   woff[5] boff[5] wide_off rows n slice_col(-1 = none) max_workgroups

@@ -594,6 +594,43 @@ class Sequential(tnn.Module):
             ev = self._eval_engine = MnistEvaluator(view)
         return ev if MnistEvaluator.supported(ev.model) else None
 
+    def _family_view(self):
+        """A view sharing this model's layers when the stack belongs to the E1 / E8 / E11 CNN family (Conv2D(32, k),
+        Conv2D(64, k), MaxPooling2D(p), Flatten, Dense(128, relu), Dense(10[, softmax]), Dropout layers anywhere)
+        — matched on the layers by runtime.cnn_eval.family_layers — else None."""
+        from .runtime.cnn_eval import FamilyView, family_layers
+
+        mods = [m for m in self.net if not isinstance(m, (_InputNorm, _Reshape, hnn.Flatten, hnn.Dropout))]
+        if len(mods) != 5:
+            return None
+        c1, c2, pool, f1, f2 = mods
+        if isinstance(f2, tnn.Sequential) and len(f2) == 2 and isinstance(f2[1], _Softmax):
+            f2 = f2[0]
+        v = FamilyView(c1, c2, pool, f1, f2)
+        return v if family_layers(v) is not None else None
+
+    def _family_evaluator(self, x):
+        """The one-launch evaluator of the CNN family (runtime.cnn_eval) under ``_evaluator``'s conditions (GPU,
+        one process, a whole uint8 array / tensor of 28x28(x1) images); else None.  Opt-in: HOPSX_EVAL_FAMILY=1."""
+        if self.net is None or self.device is None or self.device.type != "cuda":
+            return None
+        if not (isinstance(x, (np.ndarray, torch.Tensor)) and str(x.dtype) in ("uint8", "torch.uint8")
+                and tuple(x.shape[1:]) in ((28, 28), (28, 28, 1))):
+            return None
+        from .parallel import dist as hdist
+        from .runtime.cnn_eval import CnnFamilyEvaluator, enabled
+
+        if not enabled() or hdist.world_size() > 1:  # (off: nothing below runs, the route is the parent's)
+            return None
+        ev = getattr(self, "_family_engine", None)
+        if ev is None:
+            # (the flagship stack matches the family too: it stays with _evaluator and HOPSX_EVAL_FUSED)
+            view = self._family_view() if self._flagship_view() is None else None
+            if view is None or not CnnFamilyEvaluator.supported(view):
+                return None
+            ev = self._family_engine = CnnFamilyEvaluator(view)
+        return ev if CnnFamilyEvaluator.supported(ev.model) else None
+
     def _eval_resident(self, x, y=None):
         """Device copies of an evaluation set (uint8 images [N, 28, 28(, 1)], int labels or None), uploaded once
         and kept while evaluate / predict / fit's validation are called with the same arrays — a one-entry
@@ -866,11 +903,11 @@ class Sequential(tnn.Module):
         if self._step is None:
             first = next(iter(x)) if y is None else (x[:1], y[:1])
             self._prepare(_to_tensor(first[0], "cpu"))
-        # the flagship MNIST CNN on a whole uint8 set: one launch, one host read (runtime.persist_eval);
-        # batch_size plays no part there
+        # the flagship MNIST CNN (runtime.persist_eval) or a stack of the E1 / E8 / E11 family (runtime.cnn_eval) on a
+        # whole uint8 set: one launch, one host read; batch_size plays no part there
         ev = None
         if y is not None and steps is None and self._kind == "sparse_ce":
-            ev = self._evaluator(x)
+            ev = self._evaluator(x) or self._family_evaluator(x)
             if ev is not None and len(y) != len(x):
                 ev = None
         src = iter(()) if ev is not None else iter(x) if y is None else _batches(x, y, batch_size, False, None)
@@ -916,8 +953,8 @@ class Sequential(tnn.Module):
                 from .runtime.arena import ParamArena
 
                 ParamArena.from_module(self, self.device)
-        ev = self._evaluator(x)
-        if ev is not None:  # one launch over the whole set (runtime.persist_eval); batch_size plays no part
+        ev = self._evaluator(x) or self._family_evaluator(x)
+        if ev is not None:  # one launch over the whole set (runtime.persist_eval / cnn_eval); batch_size plays no part
             logits = ev.run(self._eval_resident(x)[0]).logits
             last = self.net[-1]
             if isinstance(last, _Softmax) or (isinstance(last, tnn.Sequential) and len(last)
