@@ -119,6 +119,20 @@ constexpr int HAND_WL_BWD = 1 << 6;  // pool backward -> conv2 wgrad -> C part 1
 #else
 #define HOPSX_WL_HAND(a) ((a).hand)
 #endif
+// The positions' VALU work on element pairs (position_wg; profiles/r23_persist_pack.txt, HOPSX_PERSIST_PACK, one bit
+// per part).  One wave per SIMD runs this code, so every VALU instruction's issue time is on the step's chain: where
+// a thread's two adjacent elements take the same operation, one packed instruction (v_pk_fma_f32, one packed bf16
+// convert, one 32-bit LDS store) stands for two scalar ones.  Each half is the same IEEE operation on the same operands
+// in the same order, so no bit changes; 0 is the parent's path
+constexpr int HAND_PK_C1 = 1 << 26;  // conv1 on channel pairs: thread -> (channels 2cp, 2cp + 1; images 2bg, 2bg + 1)
+// -DHOPSX_PERSIST_PACK_FIXED=n (tools/persist_isa.py only), as HOPSX_PERSIST_WLOCAL_FIXED above
+#ifdef HOPSX_PERSIST_PACK_FIXED
+#define HOPSX_PK_HAND(a) (((HOPSX_PERSIST_PACK_FIXED) & 1) << 26)
+#else
+#define HOPSX_PK_HAND(a) ((a).hand)
+#endif
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
 constexpr int NLINE_A = (NPOS + 31) / 32;  // 128-byte lines of the A flag row
 // the 32 lane-owned fc1 updates of a step in chunks of FCH, in the order of the whole update (ii, j, r).  A chunk has
 // to stay well below a flag round trip (it runs between a poll's loads and the ballot that consumes them): 4 updates
@@ -228,7 +242,8 @@ struct Args {
   // (HOPSX_PERSIST_FILL, HAND_FILL_*); bits 20..23: chunks of the fc1 update the owners may run inside the C wait
   // (HOPSX_PERSIST_FILL_MAX); bits 18..19: the gate in front of the heads' A wait (HOPSX_PERSIST_GATE_A); bits 24..25:
   // the one-wave head's operands in registers, its logits by wave_sum_tree (HOPSX_PERSIST_HEAD_CHAIN, HAND_HEAD_*);
-  // bits 4..6: the positions' wave-local staging (HOPSX_PERSIST_WLOCAL, HAND_WL_*)
+  // bits 4..6: the positions' wave-local staging (HOPSX_PERSIST_WLOCAL, HAND_WL_*); bits 26..28: the positions'
+  // VALU work on element pairs (HOPSX_PERSIST_PACK, HAND_PK_*; bit 26 is the one part in the tree)
   int hand;
   int gate_a_tk;  // wall-clock ticks the A gate watches its line before it gives way to the full wait (_GATE_A_US)
   float inv_gb;   // 1 / global batch (world * B): the loss is the mean over every replica's images
@@ -664,13 +679,46 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
     stamp(a, s, 0);
     XIN[xb * 16 + xr * 4 + 2 * xh] = (float)(xv & 0xFFu) * a.xscale + a.xshift;
     XIN[xb * 16 + xr * 4 + 2 * xh + 1] = (float)(xv >> 8) * a.xscale + a.xshift;
-    // XIN fill -> conv1 is wave-local: xb = tid >> 3 writes images 8w .. 8w + 7, conv1's bg = tid >> 5 reads images
-    // 8w .. 8w + 7.  XIN's cross-wave readers are the conv1 weight gradient (images 16 mh ..), behind the barrier in
-    // front of the fc1 partial product below, and it ends before the barrier behind RED; CW1 / CB1 were written
-    // behind the D load's barrier
+    // XIN fill -> conv1 is wave-local: xb = tid >> 3 writes images 8w .. 8w + 7, conv1's bg = tid >> 5 (4 images a
+    // thread; on channel pairs bg = tid >> 4, 2 images a thread) reads images 8w .. 8w + 7.  XIN's cross-wave readers
+    // are the conv1 weight gradient (images 16 mh ..), behind the barrier in front of the fc1 partial product below,
+    // and it ends before the barrier behind RED; CW1 / CB1 were written behind the D load's barrier
     wave_or_wg(HOPSX_WL_HAND(a) & HAND_WL_FWD);
     // ---- conv1 (VALU): 32 images x 3x3 positions x 32 channels ----
-    {
+    if (HOPSX_PK_HAND(a) & HAND_PK_C1) {
+      // channel pairs: a thread owns channels 2cp, 2cp + 1 of images 2bg, 2bg + 1 (wave w: bg = 4w .. 4w + 3, images
+      // 8w .. 8w + 7 as before).  An output pair is 4 v_pk_fma_f32 (the patch value in both halves), 2 max, one
+      // packed convert and one 32-bit store: the same fused multiply-adds in the same order as the scalar form below
+      const int cp = tid & 15, bg = tid >> 4;
+      const f32x4 ka = *(const f32x4*)(CW1 + cp * 8), kb = *(const f32x4*)(CW1 + cp * 8 + 4);
+      const f32x2 k0 = {ka[0], kb[0]}, k1 = {ka[1], kb[1]}, k2 = {ka[2], kb[2]}, k3 = {ka[3], kb[3]};
+      const f32x2 bias = *(const f32x2*)(CB1 + 2 * cp);
+      f32x4 xq[2][4];  // the 4x4 patches of this thread's 2 images, all in flight before the first use
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xq[u][c] = *(const f32x4*)(XIN + (bg * 2 + u) * 16 + 4 * c);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int b = bg * 2 + u;
+        const f32x4* xi = xq[u];
+#pragma unroll
+        for (int py = 0; py < 3; ++py)
+#pragma unroll
+          for (int px = 0; px < 3; ++px) {
+            f32x2 v = bias;
+            v = __builtin_elementwise_fma((f32x2){xi[py][px], xi[py][px]}, k0, v);
+            v = __builtin_elementwise_fma((f32x2){xi[py][px + 1], xi[py][px + 1]}, k1, v);
+            v = __builtin_elementwise_fma((f32x2){xi[py + 1][px], xi[py + 1][px]}, k2, v);
+            v = __builtin_elementwise_fma((f32x2){xi[py + 1][px + 1], xi[py + 1][px + 1]}, k3, v);
+            v = (f32x2){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)};
+            // (4-byte aligned: L_C1 is a multiple of 16, a C1 row is C1S * 2 = 80 bytes, the pair sits 4 cp into it)
+            *(unsigned*)(C1 + (b * 9 + py * 3 + px) * C1S + 2 * cp) =
+                __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16v2));
+          }
+      }
+    } else {
       const int ci = tid & 31, bg = tid >> 5;
       const float k0 = CW1[ci * 4 + 0], k1 = CW1[ci * 4 + 1], k2 = CW1[ci * 4 + 2], k3 = CW1[ci * 4 + 3];
       const float bias = CB1[ci];
@@ -697,8 +745,9 @@ __device__ __forceinline__ void position_wg(const Args& a, unsigned char* smem, 
           }
       }
     }
-    // conv1 -> conv2 is wave-local: conv1 wrote C1 of images 8w .. 8w + 7, conv2's A fragments read images
-    // b = 4 (2w + ii) + (fr >> 2), the same ones; W2 and CB2 were written behind the D load's barrier, KEEP behind the
+    stamp(a, s, 15);  // (debug stamps: conv1 issued; splits "conv fwd" into conv1 and conv2 + epilogue)
+    // conv1 -> conv2 is wave-local: conv1, with either thread map, wrote C1 of images 8w .. 8w + 7, conv2's A fragments
+    // read images b = 4 (2w + ii) + (fr >> 2), the same ones; W2 and CB2 were written behind the D load's barrier, KEEP behind the
     // B wait's (or the D wait's) barriers.  C1 is read by every wave in the backward (cfrag, c1v) and next written by
     // the next step's conv1: the barrier behind RED, the one in front of C's part 2, the C-publish barrier and the D
     // load's barrier lie between.  POOL / AM, written below, are published by the barrier in front of the fc1 partial
@@ -1901,7 +1950,7 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   // launch knobs (environment), read once and again after hopsx_mnist_persist_reload_knobs (tools/persist_ab.py)
   static int kn_ok = 0, kn_pollw, kn_stagger, kn_a, kn_b, kn_c, kn_d, kn_head1w, kn_memset, kn_coop;
   static int kn_tagged, kn_gate, kn_poll1, kn_prog, kn_fill, kn_fmax;
-  static int kn_gate_a, kn_gate_a_tk, kn_head, kn_wlocal;
+  static int kn_gate_a, kn_gate_a_tk, kn_head, kn_wlocal, kn_pack;
   static long kn_start_ms;
   if (!kn_ok || g_persist_reload) {
     auto pw = [&](const char* name, long dflt) {
@@ -1970,6 +2019,11 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
     // all: 1 the forward up to the pooled tile without workgroup barriers, 2 A published per wave, 4 the backward
     // with one barrier and C's part 1 published per wave; 0 is the path of the build before it
     kn_wlocal = (int)(hopsx_env_int("HOPSX_PERSIST_WLOCAL", 7) & 7);
+    // the positions' VALU work on element pairs (position_wg; profiles/r23_persist_pack.txt), one bit per part: 1 conv1
+    // on channel pairs (packed fused multiply-adds, one packed convert and one 32-bit store per output pair); bits 2
+    // and 4 of the knob are reserved for the conv2 epilogue and the pool backward and select nothing; 0 is the path
+    // of the build before it
+    kn_pack = (int)(hopsx_env_int("HOPSX_PERSIST_PACK", 1) & 1);
     kn_ok = 1;
     g_persist_reload = 0;
   }
@@ -1982,7 +2036,8 @@ extern "C" int hopsx_mnist_persist(const uint64_t* p, int np, const long* iv, in
   a.head1w = kn_head1w;
   a.hand = kn_tagged | (kn_poll1 << 1) | (kn_prog << 2) | (kn_gate << 8) | (kn_fill << 16) | (kn_fmax << HAND_FMAX_SHIFT) |
            (kn_gate_a << HAND_GATEA_SHIFT) | (kn_head & 1 ? HAND_HEAD_REGS : 0) | (kn_head & 2 ? HAND_HEAD_TREE : 0) |
-           (kn_wlocal & 1 ? HAND_WL_FWD : 0) | (kn_wlocal & 2 ? HAND_WL_A : 0) | (kn_wlocal & 4 ? HAND_WL_BWD : 0);
+           (kn_wlocal & 1 ? HAND_WL_FWD : 0) | (kn_wlocal & 2 ? HAND_WL_A : 0) | (kn_wlocal & 4 ? HAND_WL_BWD : 0) |
+           (kn_pack & 1 ? HAND_PK_C1 : 0);
   g_persist_hand = a.hand;
   a.gate_a_tk = kn_gate_a_tk;
   if (kn_start_ms > 0 && kn_start_ms * 100000ll < a.tmo) a.tmo0 = kn_start_ms * 100000ll;

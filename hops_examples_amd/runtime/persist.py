@@ -62,10 +62,11 @@ def geometry() -> dict:
 def launch_knobs() -> dict:
     """What the environment's launch knobs came to in the LAST launch of this process (the host wrapper reads them
     once and again after ``mnist_persist_reload_knobs()``): the kernel's hand-off word and the parts of
-    ``HOPSX_PERSIST_WLOCAL`` (the positions' wave-local staging, bits 4..6 of it; 0 before the first launch).  One word per process, like the
+    ``HOPSX_PERSIST_WLOCAL`` (the positions' wave-local staging, bits 4..6 of it; 0 before the first launch) and of
+    ``HOPSX_PERSIST_PACK`` (their VALU work on element pairs, bits 26..28).  One word per process, like the
     knobs: with several engines it is whichever launched last."""
     hand = int(_ext().mnist_persist_hand())
-    return {"hand": hand, "wlocal": (hand >> 4) & 7}
+    return {"hand": hand, "wlocal": (hand >> 4) & 7, "pack": (hand >> 26) & 7}
 
 
 class PersistentError(RuntimeError):
@@ -557,7 +558,7 @@ class PersistentMnistStep:
         """[grid, k, 16] wall-clock stamps (100 MHz ticks) of the last launch (debug_stamps=True).
         Position workgroups: 0 step start, 1 conv fwd done, 2 A published, 3 B ready, 4 pool bwd done,
         5 conv bwd done, 6 C published, 7 C ready (slice owners), 8 D published (owners), 9 fc1 slice
-        updated, 10 D ready, 11 step end.  Heads: 0 A ready, 1 B published, 2 fc2 update done."""
+        updated, 10 D ready, 11 step end, 15 conv1 issued (between 0 and 1).  Heads: 0 A ready, 1 B published, 2 fc2 update done."""
         if self.dbg is None:
             raise RuntimeError("construct with debug_stamps=True")
         return self.dbg.view(self.geom["grid"], self.spl, 16)[:, :k]

@@ -3,11 +3,12 @@
 the step loop of position_wg at its s_barriers and wave-level ordering points and prints, per compute segment, the
 VALU / LDS / s_waitcnt / MFMA instruction counts, how many of the waits are a full `lgkmcnt(0)`, and which of the two
 stands in front of the segment (`barrier`) — for mnist_persist_k<false> and <true>, once per path of
-HOPSX_PERSIST_WLOCAL (the default and 0: compiled with -DHOPSX_PERSIST_WLOCAL_FIXED, so that each text holds one path).
+HOPSX_PERSIST_WLOCAL (the default and 0: compiled with -DHOPSX_PERSIST_WLOCAL_FIXED, so that each text holds one path),
+or with --pack once per path of HOPSX_PERSIST_PACK (-DHOPSX_PERSIST_PACK_FIXED, WLOCAL fixed at its default).
 One wave per SIMD runs this code, so every wait placed right behind its LDS read exposes the read's latency:
 the s_waitcnt column is what "keep the LDS reads in flight" lowers.
 
-usage: python tools/persist_isa.py [--src FILE] [--keep-asm OUT.s] [--resources]"""
+usage: python tools/persist_isa.py [--src FILE] [--keep-asm OUT.s] [--resources] [--pack]"""
 import argparse
 import concurrent.futures as cf
 import os
@@ -112,12 +113,20 @@ def main():
     ap.add_argument("--src", default=os.path.join(ROOT, "csrc", "ops", "mnist_persist.hip"))
     ap.add_argument("--keep-asm", default=None, help="write the assembly here")
     ap.add_argument("--resources", action="store_true", help="also print the compiler's resource-usage remarks")
+    ap.add_argument("--pack", action="store_true", help="one table per path of HOPSX_PERSIST_PACK instead of _WLOCAL")
     a = ap.parse_args()
     # one compile per path of HOPSX_PERSIST_WLOCAL (fixed at compile time: one arm of every branch on it in the text),
     # and the build's own text (the knob read at run time) for the resources
-    paths = {"7": "HOPSX_PERSIST_WLOCAL=7 (the default)", "0": "HOPSX_PERSIST_WLOCAL=0"}
+    # --pack: the same for HOPSX_PERSIST_PACK (the positions' VALU work on element pairs) with WLOCAL at its default
+    if a.pack:
+        knob, paths = "PACK", {"1": "HOPSX_PERSIST_PACK=1 (the default)", "0": "HOPSX_PERSIST_PACK=0"}
+        extra = ["-DHOPSX_PERSIST_WLOCAL_FIXED=7"]
+    else:
+        knob, paths = "WLOCAL", {"7": "HOPSX_PERSIST_WLOCAL=7 (the default)", "0": "HOPSX_PERSIST_WLOCAL=0"}
+        extra = ["-DHOPSX_PERSIST_PACK_FIXED=1"]
     with tempfile.TemporaryDirectory() as d, cf.ThreadPoolExecutor(max_workers=3) as ex:
-        jobs = {v: ex.submit(compile_asm, a.src, os.path.join(d, f"wl{v}.s"), False, [f"-DHOPSX_PERSIST_WLOCAL_FIXED={v}"])
+        jobs = {v: ex.submit(compile_asm, a.src, os.path.join(d, f"wl{v}.s"), False,
+                             [f"-DHOPSX_PERSIST_{knob}_FIXED={v}"] + extra)
                 for v in paths}
         out = a.keep_asm or os.path.join(d, "mnist_persist.s")
         log = ex.submit(compile_asm, a.src, out, True).result() if a.resources or a.keep_asm else ""
