@@ -56,14 +56,23 @@ def timed(fn, n, dev):
 
 
 def _train_loop(model, opt, kind, xs, ys, steps, warmup, dev, world, forward_fn=None, box=None, mode=None,
-                stats=None):
+                stats=None, batch=None):
     from hops_examples_amd.parallel import ps as P
-    from hops_examples_amd.runtime.step import TrainStep
+    from hops_examples_amd.runtime.step import TrainStep, make_step
 
     dp = P.make(model, opt, mode) if world > 1 else None
     if box is not None:
         box["dp"] = dp
-    st = TrainStep(model, opt, kind, dp=dp, graph=dev.type == "cuda", forward_fn=forward_fn)
+    if batch is not None and world == 1:
+        # one GPU: runtime.step.make_step picks the engine (a whole-step kernel where one takes the model)
+        st = make_step(model, opt, kind, dp=None, graph=dev.type == "cuda", batch=batch)
+    else:
+        st = TrainStep(model, opt, kind, dp=dp, graph=dev.type == "cuda", forward_fn=forward_fn)
+    whole = getattr(st, "kind", "trainstep") != "trainstep"
+    if getattr(st, "kind", None) == "mlp-step":  # (its resident epoch is read as contiguous fp32)
+        xs, ys = xs.float().contiguous(), ys.float().contiguous()
+    if stats is not None:
+        stats["engine"] = getattr(st, "kind", "trainstep")
     nb = len(xs)
     box = {}
 
@@ -75,10 +84,11 @@ def _train_loop(model, opt, kind, xs, ys, steps, warmup, dev, world, forward_fn=
     # one GPU: the epoch stays resident in HBM and steps_per_execution steps replay as ONE graph, the
     # optimizer kernel's tail copying the next batch into the input buffers (TrainStep.run_resident,
     # as bench.py's flagship) — no per-step graph launch or input copy.  HOPSX_BENCH_RESIDENT=0: per step
-    resident = (world == 1 and st.use_graph and forward_fn is None and torch.is_tensor(xs) and torch.is_tensor(ys)
-                and os.environ.get("HOPSX_BENCH_RESIDENT", "1") != "0"
-                # the in-kernel prefetch moves 16-B chunks: every batch slice a multiple of 16 bytes
-                and all(t[0].numel() * t.element_size() % 16 == 0 for t in (xs, ys)))
+    resident = (world == 1 and (whole or st.use_graph) and forward_fn is None and torch.is_tensor(xs)
+                and torch.is_tensor(ys) and os.environ.get("HOPSX_BENCH_RESIDENT", "1") != "0"
+                # the optimizer kernel's prefetch moves 16-B chunks: every batch slice a multiple of 16 bytes
+                # (a whole-step kernel stages its batches itself)
+                and (whole or all(t[0].numel() * t.element_size() % 16 == 0 for t in (xs, ys))))
     if resident:
         def run(i):
             box["r"] = st.step_resident(xs, ys)
@@ -91,7 +101,7 @@ def _train_loop(model, opt, kind, xs, ys, steps, warmup, dev, world, forward_fn=
         run.run_n = run_n
     # TrainStep runs `st.warmup` eager steps and captures the graph on the next one: warm up past the
     # capture, so the timed window holds replays only (whatever --warmup says)
-    for i in range(max(warmup, st.warmup + 2 if st.use_graph else warmup)):
+    for i in range(max(warmup, 1) if whole else max(warmup, st.warmup + 2 if st.use_graph else warmup)):
         run(i)
     if resident:
         st.prepare_resident(xs, ys, n=steps)  # capture the multi-step graphs untimed
@@ -272,7 +282,7 @@ def titanic_record(rows: int, batch: int, steps: int, warmup: int) -> dict:
     # the maggy-ablation Titanic DNN ends in Dense(1, linear); the notebook compiles it with the
     # probability-form cross-entropy (maggy-ablation-titanic-example.ipynb:415-426), whose clip has no
     # gradient outside (0, 1) — read the linear output as a logit instead, so the benchmark trains
-    el, loss = _train_loop(net, opt, "bce_logits", xs, ys, steps, warmup, dev, world, box=box, stats=lst)
+    el, loss = _train_loop(net, opt, "bce_logits", xs, ys, steps, warmup, dev, world, box=box, stats=lst, batch=B)
     dp = box.get("dp")
     if steps + warmup >= 50 and not loss < lst["initial_loss"]:  # (a 2-step rehearsal proves nothing)
         raise SystemExit(f"[titanic] the model did not learn: loss {lst['initial_loss']:.4f} -> {loss:.4f}")
@@ -282,7 +292,7 @@ def titanic_record(rows: int, batch: int, steps: int, warmup: int) -> dict:
              "shard_mode": getattr(td, "last_shard_mode", None), "final_loss": round(loss, 4),
              "initial_loss": round(lst["initial_loss"], 4), "normalised": "td statistics (mean / stdDev)",
              "loss": "sigmoid cross-entropy on the linear output",
-             "dtype": "bf16" if dev.type == "cuda" else "fp32"}
+             "dtype": "bf16" if dev.type == "cuda" else "fp32", "engine": lst.get("engine")}
     if dp is not None and hasattr(dp, "verify_replicas"):
         extra["replicas_identical"] = dp.verify_replicas()["identical"]
     ranks = launch.gather_rank_info(dev, {"rows": int(local_rows), "ingest_s": round(ingest, 4)})

@@ -141,6 +141,19 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_taxi_step2(a.p.data(), (int)a.p.size(), a.iv.data(), (int)a.iv.size(), a.fv.data(), (int)a.fv.size(),
                             a.extra, st);  // extra: the wide table's rows
   });
+  // the one-workgroup training step of the small Dense stacks (runtime/mlp_step.py)
+  m.def("mlp_step_ok", [](std::vector<long> iv) { return hopsx_mlp_step_ok(iv.data(), (int)iv.size()); });
+  m.def("mlp_step_geom", [](std::vector<long> iv) {
+    std::vector<long> g(5, -1);
+    if (hopsx_mlp_step_geom(iv.data(), (int)iv.size(), g.data())) g.clear();
+    return g;
+  });
+  m.def("mlp_step", [](std::vector<uint64_t> p, std::vector<long> iv, std::vector<float> fv, u st) {
+    return hopsx_mlp_step(p.data(), (int)p.size(), iv.data(), (int)iv.size(), fv.data(), (int)fv.size(), S(st));
+  });
+  def_arg_slots<false>(m, "mlp_step", [](const ArgSlots& a, hipStream_t st) {
+    return hopsx_mlp_step(a.p.data(), (int)a.p.size(), a.iv.data(), (int)a.iv.size(), a.fv.data(), (int)a.fv.size(), st);
+  });
   m.def("widedeep_step_lds", [](std::vector<long> iv) { return hopsx_widedeep_step_lds(iv.data(), (int)iv.size()); });
   m.def("set_deterministic", [](int on) {
     int e = 0;

@@ -148,6 +148,14 @@ long hopsx_taxi_step2_ok(const long* iv, int ni, long rows);
 void hopsx_taxi_step2_xgeom(long* g);
 int hopsx_taxi_step2(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, long rows,
                      hipStream_t st);
+// ---- small Dense stacks (Titanic DNN, simulated MLP, maggy regressor): nsteps whole Adam / AdamW training steps
+// in one workgroup, geometry from a runtime layer table (mlp_step.hip) ----
+// iv: L B nbatch nsteps kind(1 adam, 2 adamw) loss(0 bce_logits, 1 mse) dims[L+1] acts[L] woff[L] boff[L]
+// _ok: the launch's LDS bytes or -1 (declined); _geom g: LDS bytes, state in LDS, batch tiles, trace elements,
+// trace image elements
+long hopsx_mlp_step_ok(const long* iv, int ni);
+int hopsx_mlp_step_geom(const long* iv, int ni, long* g);
+int hopsx_mlp_step(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf, hipStream_t st);
 // ---- flagship MNIST CNN: nsteps whole training steps in one persistent launch (mnist_persist.hip) ----
 int hopsx_mnist_persist(const uint64_t* ptrs, int np, const long* iv, int ni, const float* fv, int nf,
                         hipStream_t st);

@@ -527,6 +527,22 @@ class Sequential(tnn.Module):
         eng = make_step(view, self.optimizer, self._kind, dp="auto", graph=True, batch=int(batch_size))
         return eng if getattr(eng, "kind", None) == "persistent" else None
 
+    def _mlp_engine(self, batch_size):
+        """The one-workgroup whole-step engine (runtime.mlp_step, the one ``runtime.step.make_step`` picks) for fit's
+        resident-epoch path when this model is a Dense-only stack it takes at this batch size; else None."""
+        c = getattr(self, "_mlp", None)
+        key = (int(batch_size), id(self._step), os.environ.get("HOPSX_MLP_STEP", "1"))
+        if c is None or c[0] != key:
+            from .parallel import dist as hdist
+            from .runtime import mlp_step
+
+            eng = None
+            if (self.device.type == "cuda" and key[2] != "0"
+                    and mlp_step.why_not(self, self.optimizer, self._kind, int(batch_size), hdist.world_size()) is None):
+                eng = mlp_step.FusedMlpStep(self, self.optimizer, self._kind)
+            self._mlp = c = (key, eng)
+        return c[1]
+
     def _prepare(self, xb):
         if self.net is None:
             self.build(tuple(xb.shape[1:]))
@@ -662,7 +678,7 @@ class Sequential(tnn.Module):
             j = idx[s:s + batch_size]
             yield xs.index_select(0, j), ys.index_select(0, j)
 
-    def _fit_epoch_resident(self, x, y, batch_size, shuffle, rng):
+    def _fit_epoch_resident(self, x, y, batch_size, shuffle, rng, eng=None):
         """One epoch of the multi-kernel TrainStep on device-resident data: the epoch's shuffled batches are
         written into ONE persistent [nbatch, B, ...] buffer (so the captured multi-step graphs and the
         optimizer's next-batch prefetch stay bound to it), then ``run_resident`` replays
@@ -674,6 +690,10 @@ class Sequential(tnn.Module):
         if c is None or c[0] != key:
             self._res_any = c = (key, _to_tensor(x, self.device), _to_tensor(y, self.device, label=True))
         xs_all, ys_all = c[1], self._labels(c[2])
+        # Dense-only stack on floating-point features: the full batches on the one-launch engine (integer inputs
+        # keep the TrainStep: _InputNorm scales uint8 by 1 / 255 and the engine stages its batches unscaled)
+        if eng is not None and xs_all.dim() == 2 and xs_all.is_floating_point() and ys_all.shape[1:] == (1,):
+            st, xs_all = eng, xs_all.float()
         N, B = xs_all.shape[0], int(batch_size)
         nb = N // B
         buf = getattr(self, "_ep_buf", None)
@@ -692,8 +712,11 @@ class Sequential(tnn.Module):
         torch.index_select(ys_all, 0, idx[: nb * B], out=ys.view((nb * B,) + tuple(ys_all.shape[1:])))
         # the epoch starts at its first batch: the graph's static input buffers hold the batch the next
         # replay trains on (the previous epoch's prefetch), so they are refilled and the cursor reset
-        st._rn = 0
-        if st._cursor is not None and st._sx is not None and not isinstance(st._sx, (tuple, list)):
+        if st is eng:
+            eng.cursor.zero_()
+        else:
+            st._rn = 0
+        if st is not eng and st._cursor is not None and st._sx is not None and not isinstance(st._sx, (tuple, list)):
             st._sx.copy_(xs[0])
             st._sy.copy_(ys[0])
             st._cursor.zero_()
@@ -709,7 +732,7 @@ class Sequential(tnn.Module):
         st.run_resident(xs, ys, nb, on_out=on_out)
         if N > nb * B:
             j = idx[nb * B:]
-            r = st(xs_all.index_select(0, j), ys_all.index_select(0, j))
+            r = self._step(xs_all.index_select(0, j), ys_all.index_select(0, j))  # (the partial batch: TrainStep)
             tot_l.add_(r["loss"].reshape(()), alpha=N - nb * B)
             if r.get("correct") is not None:
                 tot_c.add_(r["correct"].reshape(()))
@@ -814,7 +837,8 @@ class Sequential(tnn.Module):
                     tl, tcor, tn = self._fit_epoch_fast(x, y, shuffle, rng)
                     width = 1
                 else:
-                    tl, tcor, tn, ys_all = self._fit_epoch_resident(x, y, batch_size, shuffle, rng)
+                    tl, tcor, tn, ys_all = self._fit_epoch_resident(x, y, batch_size, shuffle, rng,
+                                                                    eng=self._mlp_engine(batch_size))
                     width = self._label_width(ys_all)
                 logs = {"loss": float(tl) / tn}
                 if "accuracy" in self._metrics or "acc" in self._metrics:

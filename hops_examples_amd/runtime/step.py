@@ -395,7 +395,10 @@ def make_step(model, optimizer, loss_kind: str = "sparse_ce", dp="auto", graph: 
     ``dp``: "auto" builds the engine of ``HOPSX_DP_MODE`` (``parallel.ps.make``: DataParallel, or ShardedPS
     for parameter_server, which never takes the persistent path) when the process group has > 1 rank and
     the TrainStep path is taken; None or an engine object is passed through to TrainStep as is.
-    ``engine.kind`` says which one was built ("persistent" / "trainstep")."""
+    A Dense-only stack that ``runtime.mlp_step.supported`` takes (Adam / AdamW, ``bce_logits`` / ``mse``, one GPU,
+    ``batch`` given; ``HOPSX_MLP_STEP=0`` opts out) gets the one-workgroup whole-step engine
+    (runtime/mlp_step.py FusedMlpStep).  ``engine.kind`` says which one was built ("persistent" / "mlp-step" /
+    "trainstep"); ``engine.note`` why a whole-step engine was not taken."""
     from ..parallel import dist as hdist
 
     world = hdist.world_size()
@@ -429,6 +432,18 @@ def make_step(model, optimizer, loss_kind: str = "sparse_ce", dp="auto", graph: 
         elif flagship_layers(model) is not None:
             ok, why = launchable(dev, world)
             note = f"persistent step not launchable: {why}" if not ok else "persistent step not supported here"
+    # the Dense-only stacks (Titanic DNN, simulated MLP, maggy regressor): the whole Adam step in one workgroup
+    if (batch is not None and graph and dev is not None and dev.type == "cuda" and world == 1
+            and (dp is None or (isinstance(dp, str) and dp == "auto")) and kw.get("forward_fn") is None):
+        from . import mlp_step
+
+        if mlp_step.dense_layers(model, loss_kind) is not None:
+            why = ("HOPSX_MLP_STEP=0" if os.environ.get("HOPSX_MLP_STEP", "1") == "0"
+                   else mlp_step.why_not(model, optimizer, loss_kind, int(batch), world))
+            if why is None:
+                return mlp_step.FusedMlpStep(model, optimizer, loss_kind,
+                                             steps_per_execution=int(kw.get("steps_per_execution", 32)))
+            note = f"one-launch MLP step declined: {why}"
     if isinstance(dp, str) and dp == "auto":
         from ..parallel import ps
 
