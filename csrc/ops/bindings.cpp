@@ -49,7 +49,8 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 // The declarations, set_deterministic, det_lost and dbg_read below are generated from it.
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
-#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(cnn_eval) X(taxi_eval) X(topk) X(colsort)
+#define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(cnn_eval) X(taxi_eval) X(topk) X(colsort) \
+  X(colpair)
 #define X(tag)                              \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
@@ -531,6 +532,25 @@ HX_PYMOD(HOPSX_MODNAME) {
     return hopsx_column_order_values64(P<unsigned long long>(keys), rows, cols, P<long long>(idx), m_, P<double>(out),
                                        S(st));
   });
+  m.def("column_sort_keys64", [](u keys, long rows, int cols, u pass_mask, u ws, long ws_words, long cap_bytes, int max_wg,
+                                 u st) {
+    return hopsx_column_sort_keys64(P<unsigned long long>(keys), rows, cols, P<int>(pass_mask),
+                                    P<unsigned long long>(ws), ws_words, cap_bytes, max_wg, S(st));
+  });
+  m.def("column_pair_moments64", [](u x, long rows, int cols, u pairs, int np, u part, u counts, u sums, int max_wg, u st) {
+    return hopsx_column_pair_moments64(P<double>(x), rows, cols, P<int>(pairs), np, P<unsigned long long>(part),
+                                       P<long long>(counts), P<double>(sums), max_wg, S(st));
+  });
+  m.def("column_pair_ranks64", [](u x, long rows, int cols, u pairs, int np, u sorted, u table, u heads, u dcount, u comp,
+                                  int max_wg, u st) {
+    return hopsx_column_pair_ranks64(P<double>(x), rows, cols, P<int>(pairs), np, P<unsigned long long>(sorted),
+                                     P<unsigned long long>(table), P<unsigned>(heads), P<long long>(dcount),
+                                     P<unsigned long long>(comp), max_wg, S(st));
+  });
+  m.def("column_pair_tile", []() { return hopsx_column_pair_tile(); });
+  m.def("column_pair_table_keys", []() { return hopsx_column_pair_table_keys(); });
+  m.def("column_pair_part_words", [](long rows, int np) { return hopsx_column_pair_part_words(rows, np); });
+  m.def("column_pair_head_words", [](long rows, int cols) { return hopsx_column_pair_head_words(rows, cols); });
   m.def("u8_normalize_chan", [](u x, u y, long pixels, int C, std::vector<float> scale, std::vector<float> shift,
                                 int rev, int cout, u st) {
     if ((int)scale.size() < C || (int)shift.size() < C) return -2;

@@ -6,6 +6,7 @@
 //                               A key orders as the double does: -0.0 is folded onto +0.0, then with k the bits
 //                               key = (k >> 63) ? ~k : (k | 1 << 63); every NaN becomes ~0, above +inf
 //                               (0xFFF0000000000000), so the missing values are the tail of a sorted column.
+//   hopsx_column_sort_keys64    the same passes over keys the caller encoded (uint64 [cols][rows], sorted in place).
 //   hopsx_column_runs64         over the first count[c] keys: distinct (runs), unique (runs of length 1) and the
 //                               entropy ln(n) - (sum over runs of L ln L) / n.
 //   hopsx_column_order_values64 out[c][j] = the double behind keys[c][idx[c][j]].
@@ -483,18 +484,18 @@ extern "C" long hopsx_column_sort_ws_words(long rows, int cols, long cap_bytes) 
   return colsort::layout(rows, colsort::group_cols(rows, cols, cap_bytes)).total;
 }
 
-extern "C" int hopsx_column_sort64(const double* x, long rows, int cols, unsigned long long* keys, long long* count,
-                                   int* pass_mask, unsigned long long* ws, long ws_words, long cap_bytes,
-                                   int max_workgroups, hipStream_t st) {
+// The launches of both sort entries.  x null: keys holds caller-encoded keys, so encode_k and count are left out.
+static int sort_groups(const double* x, long rows, int cols, unsigned long long* keys, long long* count, int* pass_mask,
+                       unsigned long long* ws, long ws_words, long cap_bytes, int max_workgroups, hipStream_t st) {
   using namespace colsort;
   if (rows < 0 || rows > 0x7fffffffl || cols < 0 || max_workgroups < 0) return (int)hipErrorInvalidValue;
   if (rows == 0 || cols == 0) return (int)hipSuccess;
-  if (!x || !keys || !count || !pass_mask || !ws || ((uintptr_t)ws & 7)) return (int)hipErrorInvalidValue;
+  if (!keys || !pass_mask || !ws || ((uintptr_t)ws & 7)) return (int)hipErrorInvalidValue;
   const int G = group_cols(rows, cols, cap_bytes);
   if (ws_words < layout(rows, G).total) return (int)hipErrorInvalidValue;
   const long ntiles = tiles_of(rows);
   const int R = (int)rows;
-  int e = hopsx_zero(count, (long)cols * 8, st);
+  int e = x ? hopsx_zero(count, (long)cols * 8, st) : 0;
   for (int c0 = 0, gi = 0; c0 < cols && !e; c0 += G, ++gi) {
     const int g = cols - c0 < G ? cols - c0 : G;
     const Layout l = layout(rows, g);
@@ -506,7 +507,7 @@ extern "C" int hopsx_column_sort64(const double* x, long rows, int cols, unsigne
     const dim3 grid(grid_x(ntiles, g, max_workgroups), g), block(kThreads);
     e = hopsx_zero(ghist, (long)g * kDigits * kBins * 4, st);
     if (e) break;
-    hipLaunchKernelGGL(encode_k, grid, block, 0, st, x, R, cols, c0, (uint64_t*)keys, (unsigned long long*)count);
+    if (x) hipLaunchKernelGGL(encode_k, grid, block, 0, st, x, R, cols, c0, (uint64_t*)keys, (unsigned long long*)count);
     hipLaunchKernelGGL(ghist_k, dim3(grid.x < 64u ? grid.x : 64u, g), block, 0, st, (const uint64_t*)keys, R, c0, ghist);
     hipLaunchKernelGGL(plan_k, dim3(1), block, 0, st, (const unsigned*)ghist, R, g, plan, pass_mask + gi);
     for (int p = 0; p < kDigits; ++p) {
@@ -524,6 +525,19 @@ extern "C" int hopsx_column_sort64(const double* x, long rows, int cols, unsigne
     e = (int)hipGetLastError();
   }
   return e;
+}
+
+extern "C" int hopsx_column_sort64(const double* x, long rows, int cols, unsigned long long* keys, long long* count,
+                                   int* pass_mask, unsigned long long* ws, long ws_words, long cap_bytes,
+                                   int max_workgroups, hipStream_t st) {
+  if (rows > 0 && cols > 0 && (!x || !count)) return (int)hipErrorInvalidValue;
+  return sort_groups(x, rows, cols, keys, count, pass_mask, ws, ws_words, cap_bytes, max_workgroups, st);
+}
+
+extern "C" int hopsx_column_sort_keys64(unsigned long long* keys, long rows, int cols, int* pass_mask,
+                                        unsigned long long* ws, long ws_words, long cap_bytes, int max_workgroups,
+                                        hipStream_t st) {
+  return sort_groups(nullptr, rows, cols, keys, nullptr, pass_mask, ws, ws_words, cap_bytes, max_workgroups, st);
 }
 
 // part: 3 * cols * ceil(rows / tile) 64-bit words

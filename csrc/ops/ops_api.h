@@ -325,6 +325,9 @@ int hopsx_column_stats64(const double* x, int rows, int cols, double* out_stats,
 int hopsx_column_sort64(const double* x, long rows, int cols, unsigned long long* keys, long long* count,
                         int* pass_mask, unsigned long long* ws, long ws_words, long cap_bytes, int max_workgroups,
                         hipStream_t st);
+// the same digit passes over caller-encoded keys: keys uint64 [cols][rows] is sorted in place, column by column
+int hopsx_column_sort_keys64(unsigned long long* keys, long rows, int cols, int* pass_mask, unsigned long long* ws,
+                             long ws_words, long cap_bytes, int max_workgroups, hipStream_t st);
 int hopsx_column_sort_tile();
 int hopsx_column_sort_group_cols(long rows, int cols, long cap_bytes);
 long hopsx_column_sort_ws_words(long rows, int cols, long cap_bytes);
@@ -336,6 +339,25 @@ int hopsx_column_runs64(const unsigned long long* keys, const long long* count, 
 // out[c][j] = the double behind keys[c][idx[c][j]], idx int64 [cols][m] (an index outside [0, rows) gives NaN)
 int hopsx_column_order_values64(const unsigned long long* keys, long rows, int cols, const long long* idx, int m,
                                 double* out, hipStream_t st);
+// ---- two columns at once, for the validation pair rules (colpair.hip) ----
+// x fp64 [rows][cols] as above, pairs int32 [npairs][2] column indices, all on the device.  Over the rows where both
+// values are non-NaN: counts int64 [npairs][4] = n, #(a < b), #(a == b), #(a > b); sums fp64 [npairs][5] = sum a, sum b
+// and Saa, Sbb, Sab centred about the means (a second pass).  part: hopsx_column_pair_part_words(rows, npairs) words.
+// Fixed-order sums: the same bits for any max_workgroups.  hopsx_column_pair_tile(): rows per workgroup tile.
+int hopsx_column_pair_moments64(const double* x, long rows, int cols, const int* pairs, int npairs,
+                                unsigned long long* part, long long* counts, double* sums, int max_workgroups,
+                                hipStream_t st);
+int hopsx_column_pair_tile();
+long hopsx_column_pair_part_words(long rows, int npairs);
+// sorted uint64 [cols][rows] = hopsx_column_sort64's keys of x.  table uint64 [cols][rows] receives every column's
+// distinct keys in order, dcount int64 [cols] their number (NaN is one class), comp uint64 [npairs][rows] the
+// composite key rank_a << 32 | rank_b of every row.  heads: hopsx_column_pair_head_words(rows, cols) uint32.  A table
+// of at most hopsx_column_pair_table_keys() keys is searched in LDS, a larger one through its samples there.
+int hopsx_column_pair_ranks64(const double* x, long rows, int cols, const int* pairs, int npairs,
+                              const unsigned long long* sorted, unsigned long long* table, unsigned* heads,
+                              long long* dcount, unsigned long long* comp, int max_workgroups, hipStream_t st);
+int hopsx_column_pair_table_keys();
+long hopsx_column_pair_head_words(long rows, int cols);
 // per-channel uint8 NHWC -> bf16 image normalisation (C <= 4, optional channel reversal)
 int hopsx_u8_normalize_chan(const unsigned char* x, void* y, long pixels, int C, const float* scale,
                             const float* shift, int rev, int cout, hipStream_t st);

@@ -325,10 +325,102 @@ def _order_metric(n: str, rule: Rule, o: dict):
     return o["quantile"].get(_rule_quantile(rule))
 
 
+# The rules that compare a feature with another one, legal_values=[other].  On the device route (colpair.hip) the
+# correlation and the four row comparisons of all eligible pairs come from one two-pass moments launch, and a mutual
+# information from the dense ranks of both columns: a column whose distinct values fit the rank kernel's LDS table
+# (kernels.column_pair_table_keys(), the categorical case) is searched there, a larger one through samples in LDS and
+# then in global memory; the composite keys are sorted by the order rules' sort.  Elsewhere _metric runs the numpy /
+# pandas lines below.
+_PAIR_COMPARE = {"IS_LESS_THAN": "lt", "IS_LESS_THAN_OR_EQUAL_TO": "le", "IS_GREATER_THAN": "gt",
+                 "IS_GREATER_THAN_OR_EQUAL_TO": "ge", "HAS_CORRELATION": "corr"}
+_PAIR_RULES = (*_PAIR_COMPARE, "HAS_MUTUAL_INFORMATION")
+# Rows from which validate takes the device route for the pair rules (None: only through prefill_pairs(device=...)):
+# the smallest measured size at which the device route won five of five alternating pairs against the host route
+# (tools/colpair_bench.py on one MI355X, validate with the 6 pair rules x 8 features, upload included;
+# profiles/r25_colpair.txt):
+#   rows         device      host       pairs won
+#   100,000       3.6 ms    1167.9 ms   5 of 5
+#   1,000,000    27.4 ms   15843.4 ms   5 of 5
+#   10,000,000  297.4 ms   not run      no pair measured (the host's mutual-information line builds a string per row)
+# Nothing below 100,000 rows has been measured.
+PAIR_GPU_MIN_ROWS = 100_000
+
+
+def _has_negative_zero(s: pd.Series) -> bool:
+    v = _num(s)
+    return bool((np.signbit(v) & (v == 0)).any())
+
+
+def prefill_pairs(df: pd.DataFrame, pair_rules, stats_cache: dict, device=None) -> str:
+    """The pair rules' values of every eligible (feature, other) pair from the device: ``pair_rules`` is a list of
+    ``(rule, features)``; stores ``stats_cache["_pairs"][(feature, other)] = {corr, lt, le, gt, ge[, mi]}`` and returns
+    'gpu'.  A pair is eligible when both columns pass ``order_eligible``; its mutual information also needs both
+    columns free of -0.0 (the sort folds it onto +0.0, the host route's strings do not).  Every other pair stays on
+    the host lines of ``_metric``.  On the host route ('cpu': fewer than ``PAIR_GPU_MIN_ROWS`` rows, no GPU, no
+    eligible pair) it stores nothing."""
+    use_gpu = False
+    try:
+        import torch
+
+        use_gpu = torch.cuda.is_available() and (
+            (device is not None and torch.device(device).type == "cuda")
+            or (device is None and PAIR_GPU_MIN_ROWS is not None and len(df) >= PAIR_GPU_MIN_ROWS))
+    except Exception:  # pragma: no cover
+        pass
+    if not (use_gpu and len(df)):
+        return "cpu"
+    done = stats_cache.get("_pairs", {})
+    elig, negzero, moments, mutual = {}, {}, [], []
+    for rule, feats in pair_rules:
+        other = (rule.legal_values or [None])[0]
+        for f in feats:
+            if rule.name not in _PAIR_RULES or other is None or f not in df.columns or other not in df.columns:
+                continue
+            for c in (f, other):
+                if c not in elig:
+                    elig[c] = order_eligible(df[c])
+            if not (elig[f] and elig[other]):
+                continue
+            if rule.name == "HAS_MUTUAL_INFORMATION":
+                for c in (f, other):
+                    if c not in negzero:
+                        negzero[c] = _has_negative_zero(df[c])
+                if not (negzero[f] or negzero[other]) and "mi" not in done.get((f, other), {}):
+                    mutual.append((f, other))
+            elif "corr" not in done.get((f, other), {}):
+                moments.append((f, other))
+    moments, mutual = list(dict.fromkeys(moments)), list(dict.fromkeys(mutual))
+    if not (moments or mutual):
+        return "cpu"
+    import torch
+
+    from ..ops import kernels as K
+
+    cols = list(dict.fromkeys(c for pr in moments + mutual for c in pr))
+    at = {c: j for j, c in enumerate(cols)}
+    x = np.stack([_num(df[c]) for c in cols], 1)
+    xt = torch.from_numpy(np.ascontiguousarray(x)).pin_memory().cuda(non_blocking=True)
+    out = stats_cache.setdefault("_pairs", {})
+    if moments:
+        vals = K.column_pair_values(*K.column_pair_moments64(xt, [(at[a], at[b]) for a, b in moments]))
+        for j, pr in enumerate(moments):
+            out.setdefault(pr, {}).update({k: float(v[j]) for k, v in vals.items()})
+    if mutual:
+        h = K.column_pair_entropy64(xt, [(at[a], at[b]) for a, b in mutual]).cpu().numpy()
+        for j, pr in enumerate(mutual):
+            out.setdefault(pr, {})["mi"] = float(h[j, 0]) + float(h[j, 1]) - float(h[j, 2])
+    return "gpu"
+
+
 def _metric(rule: Rule, df: pd.DataFrame, feat: str, stats_cache: dict):
     """The measured value for rule on feature (None for row-wise predicates)."""
     n = rule.name
     s = df[feat] if feat in df.columns else None
+    if n in _PAIR_RULES and s is not None and rule.legal_values:
+        v = stats_cache.get("_pairs", {}).get((feat, rule.legal_values[0]), {}).get(
+            "mi" if n == "HAS_MUTUAL_INFORMATION" else _PAIR_COMPARE.get(n))
+        if v is not None:
+            return v
     if n in _ORDER_RULES and s is not None and "order" in stats_cache.get(feat, {}):
         v = _order_metric(n, rule, stats_cache[feat]["order"])
         if v is not None:
@@ -424,6 +516,9 @@ def validate(df: pd.DataFrame, expectations: list[Expectation], validation_id: i
     order_rules = [(r, e.features) for e in expectations for r in e.rules if r.name in _ORDER_RULES]
     order_device = prefill_order(df, [f for _, fs in order_rules for f in fs],
                                  [_rule_quantile(r) for r, _ in order_rules if r.name == "HAS_APPROX_QUANTILE"], cache)
+    # one upload (large frames) over every column an eligible pair rule reads
+    pair_device = prefill_pairs(df, [(r, e.features) for e in expectations for r in e.rules if r.name in _PAIR_RULES],
+                                cache)
     results = []
     for e in expectations:
         rs = []
@@ -448,4 +543,5 @@ def validate(df: pd.DataFrame, expectations: list[Expectation], validation_id: i
     v = FeatureGroupValidation(validation_id, int(time.time() * 1000), results, commit_time)
     v.aggregates_device = cache.get("_device", "cpu")
     v.order_device = order_device
+    v.pair_device = pair_device
     return v

@@ -1504,6 +1504,60 @@ def column_runs_reference(x):
     return counts, ent
 
 
+def column_pair_moments_reference(x, pairs):
+    """``(counts int64 [P, 4] = n, #(a < b), #(a == b), #(a > b); sums longdouble [P, 5] = sum a, sum b, Saa, Sbb,
+    Sab; corr fp64 [P])`` per pair of columns of ``x`` [rows, cols] over the rows where both values are present, all in
+    ``np.longdouble`` and centred about the long-double means; ``corr`` = Sab / sqrt(Saa Sbb) rounded once, NaN for
+    n <= 1 and for a constant column."""
+    import numpy as np
+
+    a64 = _as_f64_2d(x)
+    pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+    counts = np.zeros((len(pr), 4), np.int64)
+    sums = np.zeros((len(pr), 5), np.longdouble)
+    corr = np.full(len(pr), np.nan)
+    for p, (ca, cb) in enumerate(pr):
+        a, b = a64[:, ca], a64[:, cb]
+        m = ~(np.isnan(a) | np.isnan(b))
+        a, b = a[m], b[m]
+        counts[p] = (a.size, int((a < b).sum()), int((a == b).sum()), int((a > b).sum()))
+        if a.size:
+            with np.errstate(invalid="ignore", over="ignore"):
+                al, bl = a.astype(np.longdouble), b.astype(np.longdouble)
+                d, e = al - al.sum() / a.size, bl - bl.sum() / a.size
+                sums[p] = (al.sum(), bl.sum(), (d * d).sum(), (e * e).sum(), (d * e).sum())
+                if a.size > 1 and sums[p, 2] > 0 and sums[p, 3] > 0:
+                    corr[p] = float(sums[p, 4] / np.sqrt(sums[p, 2] * sums[p, 3]))
+    return counts, sums, corr
+
+
+def column_pair_entropy_reference(x, pairs):
+    """``(entropy fp64 [P, 3] = H(a), H(b), H(a, b); counts int64 [P, 3] = the distinct classes of a, b and the
+    pair)`` per pair of columns of ``x`` [rows, cols] over ALL rows: the classes are the sort keys of
+    ``column_key_reference`` (every NaN one class, -0.0 as +0.0), the multiplicities ``np.unique``'s, the entropy
+    -sum p ln p with ``math.fsum`` (0.0 without rows)."""
+    import math
+
+    import numpy as np
+
+    keys = column_key_reference(_as_f64_2d(x))
+    pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+    ent = np.zeros((len(pr), 3), np.float64)
+    counts = np.zeros((len(pr), 3), np.int64)
+
+    def h(mult):
+        p = mult.astype(np.float64) / keys.shape[0]
+        return -math.fsum((p * np.log(p)).tolist())
+
+    if keys.shape[0]:
+        for p, (ca, cb) in enumerate(pr):
+            (_, ia, ma), (_, ib, mb) = (np.unique(keys[:, c], return_inverse=True, return_counts=True) for c in (ca, cb))
+            mab = np.unique(ia.astype(np.int64) * mb.size + ib, return_counts=True)[1]
+            ent[p] = (h(ma), h(mb), h(mab))
+            counts[p] = (ma.size, mb.size, mab.size)
+    return ent, counts
+
+
 def column_quantile_reference(x, qs):
     """fp64 [cols, len(qs)]: ``np.nanquantile`` of every column of ``x`` [rows, cols] (NaN for an empty column)."""
     import warnings

@@ -1092,6 +1092,157 @@ def column_quantiles64(order, qs):
     return out
 
 
+def column_sort_keys64(keys, max_workgroups=0, ws=None, ws_cap_bytes=0):
+    """``keys`` (int64 [cols, rows] on the GPU holding caller-encoded uint64 keys) sorted IN PLACE, every column
+    ascending as unsigned, by the digit passes of ``column_sort64``: a ``ColumnOrder`` over ``keys`` whose ``count`` is
+    ``rows`` in every column, so ``column_runs64`` reads all keys.  ``ws`` / ``ws_cap_bytes`` / ``max_workgroups`` as for
+    ``column_sort64``; every refusal is a ValueError raised before any launch."""
+    if not isinstance(keys, torch.Tensor) or keys.dim() != 2 or keys.dtype != torch.int64:
+        raise ValueError("column_sort_keys64: int64 keys [cols, rows] expected")
+    if not keys.is_cuda or not keys.is_contiguous():
+        raise ValueError("column_sort_keys64: expected a contiguous GPU tensor")
+    rows, cols, cap = _sort_dims(keys.shape[1], keys.shape[0], ws_cap_bytes, "column_sort_keys64")
+    if int(max_workgroups) < 0:
+        raise ValueError("column_sort_keys64: max_workgroups >= 0 expected")
+    need = column_sort_ws_words(rows, cols, cap)
+    if ws is not None and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.int64 or not ws.is_cuda
+                           or ws.device != keys.device or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"column_sort_keys64: ws must be a contiguous int64 tensor of at least {need} words on "
+                         f"{keys.device}")
+    ext = _C.ext()
+    gcols = int(ext.column_sort_group_cols(rows, cols, cap)) if rows and cols else 0
+    count = torch.full((cols,), rows, device=keys.device, dtype=torch.int64)
+    pass_mask = torch.zeros((cols + gcols - 1) // gcols if gcols else 0, device=keys.device, dtype=torch.int32)
+    if rows and cols:
+        if ws is None:
+            ws = torch.empty(need, device=keys.device, dtype=torch.int64)
+        check(ext.column_sort_keys64(ptr(keys), rows, cols, ptr(pass_mask), ptr(ws), ws.numel(), cap,
+                                     int(max_workgroups), stream()), "column_sort_keys64")
+    return ColumnOrder(keys, count, pass_mask, rows, cols, int(max_workgroups))
+
+
+def column_pair_tile() -> int:
+    """Rows per workgroup tile of the pair moments (csrc/ops/colpair.hip)."""
+    return int(_C.ext().column_pair_tile())
+
+
+def column_pair_table_keys() -> int:
+    """Distinct keys of a column up to which the rank kernel of ``column_pair_entropy64`` searches the column's whole
+    table in LDS; a larger table is searched through that many samples in LDS and then in global memory."""
+    return int(_C.ext().column_pair_table_keys())
+
+
+def _pair_args(x, pairs, max_workgroups, what):
+    """The checks shared by the pair launchers: (rows, cols, pairs as a host int32 [P, 2] array)."""
+    import numpy as np
+
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{what}: x [rows, cols] expected")
+    if x.dtype != torch.float64:
+        raise ValueError(f"{what}: fp64 expected, got {x.dtype}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: expected a GPU tensor")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous tensor")
+    rows, cols, _ = _sort_dims(x.shape[0], x.shape[1], 0, what)
+    if int(max_workgroups) < 0:
+        raise ValueError(f"{what}: max_workgroups >= 0 expected")
+    pr = np.asarray(pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+    if pr.size == 0:
+        pr = np.zeros((0, 2), np.int32)
+    if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+        raise ValueError(f"{what}: pairs must be integers [P, 2]")
+    if pr.size and (pr.min() < 0 or pr.max() >= cols):
+        raise ValueError(f"{what}: pair index out of range for {cols} columns")
+    return rows, cols, np.ascontiguousarray(pr, dtype=np.int32)
+
+
+def column_pair_moments64(x, pairs, max_workgroups=0):
+    """Per pair (a, b) of columns of ``x`` (fp64 [rows, cols] on the GPU, NaN = missing), over the rows where both
+    values are present: ``(counts int64 [P, 4] = n, #(a < b), #(a == b), #(a > b); sums fp64 [P, 5] = sum a, sum b,
+    Saa, Sbb, Sab)`` with the last three centred about the means in a second pass (csrc/ops/colpair.hip).  ``pairs``:
+    integers [P, 2] (list, array or tensor).  Fixed-order sums: the same bits for any ``max_workgroups``.  Every
+    refusal is a ValueError raised before any launch."""
+    rows, cols, pr = _pair_args(x, pairs, max_workgroups, "column_pair_moments64")
+    P = pr.shape[0]
+    counts = torch.zeros(P, 4, device=x.device, dtype=torch.int64)
+    sums = torch.zeros(P, 5, device=x.device, dtype=torch.float64)
+    if rows and P:
+        ext = _C.ext()
+        pd = torch.from_numpy(pr).to(x.device)
+        part = torch.empty(int(ext.column_pair_part_words(rows, P)), device=x.device, dtype=torch.int64)
+        check(ext.column_pair_moments64(ptr(x), rows, cols, ptr(pd), P, ptr(part), ptr(counts), ptr(sums),
+                                        int(max_workgroups), stream()), "column_pair_moments64")
+    return counts, sums
+
+
+def column_pair_values(counts, sums):
+    """The pair rules' values from ``column_pair_moments64`` (numpy, on the host): a dict of fp64 [P] arrays ``corr``
+    (Sab / (sqrt Saa sqrt Sbb), clipped to [-1, 1]; NaN for n <= 1 and for a constant column, as ``np.corrcoef``) and
+    the row fractions ``lt``, ``le``, ``gt``, ``ge`` (1.0 for n == 0), each one division of two integers."""
+    import numpy as np
+
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    s = sums.cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    n, lt, eq, gt = (c[:, i] for i in range(4))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        corr = np.clip(s[:, 4] / (np.sqrt(s[:, 2]) * np.sqrt(s[:, 3])), -1.0, 1.0)
+        corr = np.where(n > 1, corr, np.nan)
+        frac = {k: np.where(n > 0, v / np.maximum(n, 1), 1.0)
+                for k, v in (("lt", lt), ("le", lt + eq), ("gt", gt), ("ge", gt + eq))}
+    return {"corr": corr, **frac}
+
+
+def column_pair_ranks64(x, pairs, order):
+    """``(comp int64 [P, rows], dcount int64 [cols])``: per pair and row the composite key ``rank_a << 32 | rank_b``,
+    a rank being the index of the row's value among the distinct values of its column (NaN one class, the last; -0.0
+    as +0.0), and per column the number of those classes.  ``order``: ``column_sort64(x)``."""
+    rows, cols, pr = _pair_args(x, pairs, order.max_workgroups, "column_pair_ranks64")
+    if tuple(order.keys.shape) != (cols, rows) or order.keys.device != x.device:
+        raise ValueError("column_pair_ranks64: order must be column_sort64(x)")
+    P = pr.shape[0]
+    comp = torch.empty(P, rows, device=x.device, dtype=torch.int64)
+    dcount = torch.zeros(cols, device=x.device, dtype=torch.int64)
+    if rows and cols:
+        ext = _C.ext()
+        pd = torch.from_numpy(pr).to(x.device)
+        table = torch.empty(cols, rows, device=x.device, dtype=torch.int64)
+        heads = torch.empty(int(ext.column_pair_head_words(rows, cols)), device=x.device, dtype=torch.int32)
+        check(ext.column_pair_ranks64(ptr(x), rows, cols, ptr(pd), P, ptr(order.keys), ptr(table), ptr(heads),
+                                      ptr(dcount), ptr(comp), order.max_workgroups, stream()), "column_pair_ranks64")
+    return comp, dcount
+
+
+def column_pair_entropy64(x, pairs, max_workgroups=0, ws_cap_bytes=0, return_counts=False):
+    """fp64 [P, 3] = H(a), H(b), H(a, b) per pair of columns of ``x`` (fp64 [rows, cols] on the GPU), natural log,
+    over ALL rows with NaN as a class of its own (and -0.0 as +0.0): the terms of a mutual information
+    H(a) + H(b) - H(a, b).  The columns the pairs name are sorted once (``column_sort64``) and their run entropies
+    taken over all keys; every row gets its dense rank in both columns (``column_pair_ranks64``), and the composite
+    keys are sorted by the same digit passes (``column_sort_keys64``, in groups under ``ws_cap_bytes``) for H(a, b).
+    ``return_counts``: also int64 [P, 3], the distinct classes of a, of b and of the pair.  Integer counts and
+    fixed-order sums: the same bits for any ``max_workgroups`` and ``ws_cap_bytes``."""
+    import numpy as np
+
+    rows, cols, pr = _pair_args(x, pairs, max_workgroups, "column_pair_entropy64")
+    _sort_dims(rows, cols, ws_cap_bytes, "column_pair_entropy64")
+    P = pr.shape[0]
+    ent = torch.zeros(P, 3, device=x.device, dtype=torch.float64)
+    cnt = torch.zeros(P, 3, device=x.device, dtype=torch.int64)
+    if rows and P:
+        used, slot = np.unique(pr, return_inverse=True)
+        slot = slot.reshape(P, 2)
+        xs = x if used.size == cols else x[:, torch.from_numpy(used).to(x.device)].contiguous()
+        order = column_sort64(xs, max_workgroups=max_workgroups, ws_cap_bytes=ws_cap_bytes)
+        order.count.fill_(rows)  # the NaN keys, one tail run, are a class here
+        c1, h1 = column_runs64(order)
+        comp, _ = column_pair_ranks64(xs, slot, order)
+        c2, h2 = column_runs64(column_sort_keys64(comp, max_workgroups=max_workgroups, ws_cap_bytes=ws_cap_bytes))
+        sl = torch.from_numpy(slot).to(x.device)
+        ent = torch.stack([h1[sl[:, 0]], h1[sl[:, 1]], h2], 1)
+        cnt = torch.stack([c1[sl[:, 0], 1], c1[sl[:, 1], 1], c2[:, 1]], 1)
+    return (ent, cnt) if return_counts else ent
+
+
 def column_hist(x, mins, maxs, bins):
     rows, cols = x.shape
     hist = torch.zeros(cols, bins, device=x.device, dtype=torch.int32)
