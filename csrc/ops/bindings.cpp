@@ -110,6 +110,18 @@ HX_PYMOD(HOPSX_MODNAME) {
                       alpha, beta, act, P<void>(aux), ldaux, P<float>(colsum), P<float>(ws), ws_elems, P<void>(ay), aact,
                       P<float>(arowsum), P<unsigned>(tickets), S(st));
   });
+  m.def("gemm_path", [](u A, long lda, u B, long ldb, int M, int N, int K, int epi, u ws, long ws_elems, u ay,
+                        u tickets) {
+    std::vector<int> o(8);
+    hopsx_gemm_path(P<void>(A), lda, P<void>(B), ldb, M, N, K, epi, P<float>(ws), ws_elems, P<void>(ay),
+                    P<unsigned>(tickets), o.data());
+    return o;
+  });
+  m.def("linear_bwd_pair_path", [](int M, int N, int K, std::vector<int> pool, int dw_store) {
+    std::vector<int> o(9);
+    hopsx_linear_bwd_pair_path(M, N, K, pool.empty() ? nullptr : pool.data(), dw_store, o.data());
+    return o;
+  });
   m.def("conv2d_fwd", [](u x, u w, std::vector<int> g, int epi, u out, u bias, int act, u colsum, float xscale,
                          float xshift, u st) {
     return hopsx_conv2d_fwd(P<void>(x), P<void>(w), g.data(), epi, P<void>(out), P<float>(bias), act,

@@ -175,9 +175,16 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
 // HOPSX_DISABLE=direct_conv,pool8,rowreduce,loss_thread,splitk
 // (read on every call: a cached getenv pointer dangles once the process changes the variable — the
 // A/B tests toggle it between runs — and then decided launches from freed memory)
+// A name matches a WHOLE comma-separated token: the value "splitk_ticket" does not turn "splitk" off, "gg_n64" not
+// "gg" (a plain strstr(env, name) let every longer token switch off the names it contains).
 static inline bool hopsx_disabled(const char* name) {
   const char* env = std::getenv("HOPSX_DISABLE");
-  return env && *env && std::strstr(env, name) != nullptr;
+  if (!env || !*env) return false;
+  const size_t n = std::strlen(name);
+  auto sep = [](char c) { return c == 0 || c == ',' || c == ' '; };
+  for (const char* p = env; (p = std::strstr(p, name)) != nullptr; p += n)
+    if ((p == env || sep(p[-1])) && sep(p[n])) return true;
+  return false;
 }
 // integer tuning knob from the environment: host-side launch sizing only.  The function itself reads the
 // variable on every call, but most callers keep the result in a function-local static (norm.hip's

@@ -572,7 +572,9 @@ __device__ __forceinline__ void mfma_gemm_body(const AL& al, const BL& bl, const
   const int m0 = tm * BM, n0 = tn * BN;
   const int kbeg = by * kps;
   const int kend = min(K, kbeg + kps);
-  if (kbeg >= kend) return;
+  // (K == 0, dense launcher only: a zero-length reduction reads nothing, every DenseLoader load is out of
+  // [0, kend), and still runs the epilogue; launch_gemm never passes it for the conv loaders)
+  if (kbeg >= kend && K > 0) return;
   const int nt = (kend - kbeg + BK - 1) / BK;
 
   bf16x8 ra[A_PT], rb[B_PT];
@@ -891,7 +893,8 @@ __device__ __forceinline__ void mfma_gemm_body(const AL& al, const BL& bl, const
           ((bf16_raw*)f.out)[(long)m * f.ldo + n] = f2bf(v);
         } else {
           float* o = (float*)f.out + (long)m * f.ldo + n;
-          *o = (f.beta != 0.f) ? v + f.beta * *o : v;
+          if (f.beta != 0.f) v += f.beta * *o;  // (the column sum takes the stored value, as EpiStoreF32)
+          *o = v;
         }
       }
       csum += v;
@@ -937,9 +940,10 @@ struct GemmPlan {
   int kps;    // K per split (multiple of BK)
 };
 
-inline GemmPlan plan_gemm(long M, long N, long K, bool allow_split, int num_cu = 256) {
+// ignore_det: the plan the shape would get outside deterministic mode (the route reporters' "det" field only)
+inline GemmPlan plan_gemm(long M, long N, long K, bool allow_split, int num_cu = 256, bool ignore_det = false) {
   GemmPlan p;
-  if (hopsx_deterministic()) allow_split = false;  // one producer per output element
+  if (hopsx_deterministic() && !ignore_det) allow_split = false;  // one producer per output element
   const long t128 = ((M + 127) / 128) * ((N + 127) / 128);
   const long t64 = ((M + 63) / 64) * ((N + 63) / 64);
   // A/B knobs (host side, read once): HOPSX_GEMM_T64_MIN / _T128_MIN = the tile count below which a
@@ -989,12 +993,12 @@ inline GemmPlan plan_gemm(long M, long N, long K, bool allow_split, int num_cu =
   return p;
 }
 
+// Launch with a plan the caller already holds (gemm.hip: launcher and route reporter share one decision).
 template <bool A_KC, bool B_KC, class AL, class BL, class EP>
-inline void launch_gemm(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, bool allow_split,
-                        hipStream_t st, float* rowsum_a = nullptr) {
+inline void launch_gemm_plan(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, const GemmPlan& p,
+                             hipStream_t st, float* rowsum_a = nullptr) {
   if (M <= 0 || N <= 0) return;
-  if (K <= 0) K = 1;  // degenerate: zero-length reduction still runs the epilogue
-  GemmPlan p = plan_gemm(M, N, K, allow_split);
+  if (K < 0) K = 0;  // degenerate: a zero-length reduction reads no operand and still runs the epilogue
   const int bm = p.cfg == 0 ? 128 : (p.cfg == 1 ? 64 : 32);
   const long tiles = (long)((M + bm - 1) / bm) * ((N + bm - 1) / bm);
   dim3 grid((unsigned)tiles, (unsigned)p.split);
@@ -1012,6 +1016,16 @@ inline void launch_gemm(const AL& al, const BL& bl, const EP& ep, int M, int N, 
                          M, N, K, p.kps, rowsum_a);
       break;
   }
+}
+
+template <bool A_KC, bool B_KC, class AL, class BL, class EP>
+inline void launch_gemm(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, bool allow_split,
+                        hipStream_t st, float* rowsum_a = nullptr) {
+  if (M <= 0 || N <= 0) return;  // (plan_gemm divides by the tile count)
+  // The conv launchers come through here: they keep the clamp (a conv K is never 0; the K == 0 contract of
+  // launch_gemm_plan, "no operand is read", is verified for DenseLoader only, which gemm.hip uses).
+  if (K <= 0) K = 1;
+  launch_gemm_plan<A_KC, B_KC>(al, bl, ep, M, N, K, plan_gemm(M, N, K, allow_split), st, rowsum_a);
 }
 
 inline int is_vec_ok(const void* p, long ld) { return (ld % 8 == 0) && ((uintptr_t)p % 16 == 0); }

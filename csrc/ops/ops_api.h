@@ -19,6 +19,14 @@ int hopsx_gemm(const void* A, long lda, int a_kc, const void* B, long ldb, int b
                void* out, long ldo, const float* bias, float alpha, float beta, int act, const void* aux, long ldaux,
                float* colsum, float* ws, long ws_elems, const void* ay, int aact, float* arowsum, unsigned* tickets,
                hipStream_t st);
+// What hopsx_gemm runs for exactly these routing arguments, nothing launched (launcher and reporter share one
+// decision function, gemm.hip gemm_route).  Return value = out[0]: 0 direct (one GEMM, the caller's epilogue, K
+// unsplit), 1 atomic (EPI_ATOMIC_F32, K split as planned), 2 ticket (split-K into ws with the in-launch finish),
+// 3 finish (memset + atomic split-K GEMM + splitk_finish_k: no ticket counters, or HOPSX_DISABLE=splitk_ticket).
+// out[8] (may be null) = {route, tile edge 128 / 64 / 32, K split, K per split, output tiles (gridDim.x), A loaded
+// by 16-byte vectors, B likewise, deterministic mode took a K split away}.
+int hopsx_gemm_path(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int epi, const float* ws,
+                    long ws_elems, const void* ay, const unsigned* tickets, int* out);
 // xscale != 0: x is uint8 and is read as x * xscale + xshift (input-layer normalisation fused; direct kernel only)
 // a Linear layer's dgrad + wgrad (+ bias grad) in one launch; -2: unsupported shape (gemm.hip)
 // pool (optional) = {C, PH, PW, KH, KW, act}: x came from a non-overlapping max-pool and dx is the
@@ -30,6 +38,11 @@ int hopsx_linear_bwd_pair(const void* dy, const void* w, const void* x, void* dx
                           const int* pool, const unsigned char* pool_am, const void* pool_x,
                           const unsigned long long* pool_rng, unsigned pool_salt, float pool_p, int dw_store,
                           hipStream_t st);
+// The pair launcher's decision, nothing launched (gemm.hip pair_route, shared with the launcher).  Return value =
+// out[0]: 0 one launch, -2 separate launches, -3 pool geometry refused.  out[9] (may be null) = {code, dgrad tile
+// edge, wgrad tile edge, dgrad gridDim.y (1), wgrad K split, dW by plain stores, pool-scatter epilogue, dgrad tiles,
+// wgrad tiles}.
+int hopsx_linear_bwd_pair_path(int M, int N, int K, const int* pool, int dw_store, int* out);
 int hopsx_conv2d_fwd(const void* x, const void* w, const int* geom, int epi, void* out, const float* bias, int act,
                      float* colsum, float xscale, float xshift, hipStream_t st);
 // y/yact: this conv's activation output -> fused act' mask on dY (prologue fusion)

@@ -34,7 +34,8 @@ Performance / communication knobs read where they act:
   HOPSX_BN_COOP         1 = one-launch BN backward with a grid barrier (measured slower; off)
   HOPSX_DGRAD_XCD       1 = XCD-aware block order in the direct MFMA dgrad (measured neutral; off)
   HOPSX_DISABLE         comma list of fast paths to turn off for A/B checks, e.g. bnstats, bn_defer,
-                        ks5, bwd_pair, conv_mfma, wgrad_mfma, blaslt_1x1, direct_conv
+                        ks5, bwd_pair, conv_mfma, wgrad_mfma, blaslt_1x1, direct_conv (the native side
+                        matches whole tokens: splitk_ticket does not turn splitk off, gg_n64 not gg)
 """
 from __future__ import annotations
 

@@ -1325,6 +1325,74 @@ def dense_reference(x, w, b=None, act=None, dtype=torch.float64):
             "tanh": torch.tanh}[act](y)
 
 
+def _act_grad_from_out(y, name):
+    """common.h act_grad_from_out: the activation's derivative expressed through its OUTPUT ``y``."""
+    return {None: lambda v: torch.ones_like(v), "relu": lambda v: (v > 0).to(v.dtype),
+            "sigmoid": lambda v: v * (1 - v), "tanh": lambda v: 1 - v * v}[name](y)
+
+
+def gemm_reference(a, b, a_kc=True, b_kc=True, epi="store", alpha=1.0, bias=None, act=None, beta=0.0, old=None,
+                   aux=None, a_mask_y=None, a_mask_act=None, dtype=torch.float64):
+    """Plain-tensor statement of gemm.hip hopsx_gemm on the host, from the bf16 operands as given.  ``a`` is
+    [M, K] (``a_kc``) or [K, M], ``b`` is [N, K] (``b_kc``) or [K, N].  With ``a_mask_y`` (layout of ``a``) the A
+    operand is ``bf16(a * act'(a_mask_y))``: the kernels' one rounding point, before the product.  With
+    ``acc = A B^T`` [M, N] in ``dtype``, ``epi`` selects
+
+    * ``"store"``:  ``act(alpha acc + bias) + beta old`` (the bf16 store has no ``beta`` term),
+    * ``"atomic"``: ``old + alpha acc``,
+    * ``"dact"``:   ``acc * act'(aux)``, ``act'`` through the activation's output ``aux`` [M, N].
+
+    Returns ``(out, colsum, rowsum)``, all unrounded: ``colsum`` [N] sums over M the value the epilogue hands to the
+    column sum (``out`` itself; for ``"atomic"`` the increment ``alpha acc``), ``rowsum`` [M] sums the masked A
+    operand over K (the bias gradient of a weight-gradient GEMM, where A = dY^T)."""
+    d = lambda t: t.to(dtype)  # noqa: E731
+    am = d(a)
+    if a_mask_y is not None and _act_name(a_mask_act) is not None:
+        am = d((am * _act_grad_from_out(d(a_mask_y), _act_name(a_mask_act))).to(torch.bfloat16))
+    A = am if a_kc else am.t()
+    B = d(b) if b_kc else d(b).t()
+    acc = A @ B.t()
+    name = _act_name(act)
+    if epi == "atomic":
+        inc = alpha * acc
+        out, cs = (inc if old is None else d(old) + inc), inc
+    elif epi == "dact":
+        out = acc if aux is None else acc * _act_grad_from_out(d(aux), name)
+        cs = out
+    else:
+        v = alpha * acc
+        if bias is not None:
+            v = v + d(bias)
+        out = {None: lambda t: t, "relu": torch.relu, "sigmoid": torch.sigmoid, "tanh": torch.tanh}[name](v)
+        if beta != 0.0:
+            out = out + beta * d(old)
+        cs = out
+    return out, cs.sum(0), A.sum(1)
+
+
+def linear_bwd_reference(dy, w, x, y=None, act=None, yprev=None, act_prev=None, pool=None, dtype=torch.float64):
+    """The backward of ``y = act(x w^T + b)`` as the dense launchers state it (linear_dgrad / linear_wgrad /
+    linear_bwd_pair), built on gemm_reference: with ``g = bf16(dy * act'(y))`` returns ``(dx, dw, dbias)`` =
+    ``(g w * act_prev'(yprev), g^T x, sum_m g)``, unrounded.  ``pool`` = (argmax, premask, in_shape, (KH, KW), act,
+    rng, salt, p) as kernels.linear_bwd_pair takes it: ``x`` is the flattened output of a non-overlapping floor-mode
+    max-pool, and ``dx`` is the gradient of the POOL INPUT [B, H, W, C]: ``g w``, times the fused Dropout's keep mask
+    / (1 - p) (dropout_keep_reference), times ReLU' read off the pooled value ``x`` (``premask``), scattered to the
+    argmax taps by pool_bwd_reference."""
+    dx, _, _ = gemm_reference(dy, w, True, False, "dact", act=act_prev, aux=yprev, a_mask_y=y, a_mask_act=act,
+                              dtype=dtype)
+    dw, _, db = gemm_reference(dy, x, False, False, "atomic", a_mask_y=y, a_mask_act=act, dtype=dtype)
+    if pool is not None:
+        am, premask, in_shape, k, _pact, rng, salt, p = pool[:8]
+        B, H, W, C = in_shape
+        PH, PW = H // k[0], W // k[1]
+        g = dx.view(B, PH, PW, C)
+        if premask:
+            g = g * (x.view(B, PH, PW, C) > 0).to(dtype)
+        mask = dropout_keep_reference(rng, salt, (B, PH, PW, C), p) if p > 0 else None
+        dx, _ = pool_bwd_reference(g, am.view(B, PH, PW, C), in_shape, k, k, 0, mask=mask, drop_p=p, dtype=dtype)
+    return dx, dw, db
+
+
 def dropout_reference(h, mask, p: float):
     """The bf16 tensor a Dropout hands on: ``bf16(h * mask / (1 - p))``, the product formed in fp32 as
     elementwise.hip dropout_k forms it (``mask`` from the project's generator: ``K.dropout(ones, ...) != 0``)."""

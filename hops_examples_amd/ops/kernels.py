@@ -44,6 +44,20 @@ def gemm_raw(a, lda, a_kc, b, ldb, b_kc, M, N, K, epi, out, ldo, bias=None, alph
     check(rc, "gemm")
 
 
+GEMM_ROUTES = ("direct", "atomic", "ticket", "finish")
+
+
+def gemm_path(a, lda, b, ldb, M, N, K, epi, ws=None, a_mask_y=None) -> dict:
+    """What gemm_raw runs for these routing arguments, nothing launched (gemm.hip gemm_route, the launcher's own
+    decision): ``route`` direct / atomic / ticket / finish, ``tile`` 128 / 64 / 32, ``split`` and ``kps`` (K per
+    split), ``grid`` (output tiles), ``avec`` / ``bvec`` (16-byte operand loads) and ``det`` (deterministic mode took
+    a K split away)."""
+    v = _C.ext().gemm_path(ptr(a), lda, ptr(b), ldb, M, N, K, epi, ptr(ws), 0 if ws is None else ws.numel(),
+                           ptr(a_mask_y), ptr(ticket(a.device)) if ws is not None else 0)
+    return dict(route=GEMM_ROUTES[v[0]], tile=v[1], split=v[2], kps=v[3], grid=v[4], avec=bool(v[5]), bvec=bool(v[6]),
+                det=bool(v[7]))
+
+
 _SPLITK_WS: dict = {}
 
 
@@ -105,6 +119,27 @@ def linear_wgrad(dy, x, dw, alpha=1.0, y=None, act=0, dbias=None):
     return dw
 
 
+def _pool_vec(pool) -> list:
+    """linear_bwd_pair's ``pool`` tuple -> the launcher's {C, PH, PW, KH, KW, act, H, W} ([] without a pool)."""
+    if pool is None:
+        return []
+    _, xin, (_, H, W, C), (kh, kw), pact = pool[:5]
+    return [C, H // kh, W // kw, kh, kw, act_id(pact) if xin else 0, H, W]
+
+
+PAIR_ROUTES = {0: "pair", -2: "separate", -3: "refuse"}
+
+
+def linear_bwd_pair_path(M, N, K, pool=None, dw_store=False) -> dict:
+    """What linear_bwd_pair does for dy [M, N], w [N, K] and these options, nothing launched (gemm.hip pair_route,
+    the launcher's own decision): ``route`` pair / separate (returns False) / refuse (raises); ``bma`` / ``bmb`` the
+    tile edges of the dgrad and the wgrad part, ``gyA`` / ``gyB`` their K splits, ``dw`` store / atomic, ``epilogue``
+    dact / pool."""
+    v = _C.ext().linear_bwd_pair_path(M, N, K, _pool_vec(pool), int(bool(dw_store)))
+    return dict(route=PAIR_ROUTES[v[0]], bma=v[1], bmb=v[2], gyA=v[3], gyB=v[4], dw="store" if v[5] else "atomic",
+                epilogue="pool" if v[6] else "dact", gxA=v[7], gxB=v[8])
+
+
 def linear_bwd_pair(dy, w, x, dw, y=None, act=0, dbias=None, pool=None, dw_store=False):
     """dX and dW (+ dbias) of a Linear layer in ONE launch (gemm.hip linear_bwd_pair_k); returns
     dX [M, K] bf16, or False when the shape goes to the separate launches (small-M split-K dgrad).
@@ -119,11 +154,10 @@ def linear_bwd_pair(dy, w, x, dw, y=None, act=0, dbias=None, pool=None, dw_store
     _req(x, BF16, "x")
     _req(w, BF16, "w")
     _req(dw, F32, "dw")
-    pl, pam, px, prng, psalt, pp = [], 0, 0, 0, 0, 0.0
+    pl, pam, px, prng, psalt, pp = _pool_vec(pool), 0, 0, 0, 0, 0.0
     if pool is not None:
-        am, xin, in_shape, (kh, kw), pact, rng, salt, p = pool[:8]
+        am, xin, in_shape, _, _, rng, salt, p = pool[:8]
         B, H, W, C = in_shape
-        pl = [C, H // kh, W // kw, kh, kw, act_id(pact) if xin else 0, H, W]
         pam, px, prng, psalt, pp = ptr(am), (ptr(x) if xin else 0), ptr(rng), int(salt) & 0xFFFFFFFF, float(p)
         dx = torch.empty(B, H, W, C, device=dy.device, dtype=BF16)
     else:

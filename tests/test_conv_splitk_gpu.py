@@ -59,8 +59,9 @@ def test_conv_fwd_dgrad_splitk(shape):
         torch.cuda.synchronize()
         _close(y, yref)
         _close(dx, dxref)
-    y0 = _with("conv_splitk", lambda: K.conv2d_fwd(x, w, g))
-    dx0 = _with("conv_splitk", lambda: K.conv2d_dgrad(dy, w, g))
+    # (whole tokens: "conv_splitk" used to switch the dense "splitk" off as well, by substring)
+    y0 = _with("conv_splitk,splitk", lambda: K.conv2d_fwd(x, w, g))
+    dx0 = _with("conv_splitk,splitk", lambda: K.conv2d_dgrad(dy, w, g))
     _close(y, y0, 1e-2)
     _close(dx, dx0, 1e-2)
 
