@@ -50,8 +50,8 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
 #define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(cnn_eval) X(taxi_eval) X(topk) X(colsort) \
-  X(colpair)
-#define X(tag)                              \
+  X(colpair) X(groupagg)
+#define X(tag)                             \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
 HOPSX_DET_TUS(X)
@@ -563,6 +563,25 @@ HX_PYMOD(HOPSX_MODNAME) {
   m.def("column_pair_table_keys", []() { return hopsx_column_pair_table_keys(); });
   m.def("column_pair_part_words", [](long rows, int np) { return hopsx_column_pair_part_words(rows, np); });
   m.def("column_pair_head_words", [](long rows, int cols) { return hopsx_column_pair_head_words(rows, cols); });
+  m.def("group_keys64", [](u x, long rows, int cols, std::vector<int> key_cols, std::vector<long long> classes, u comp,
+                           u keys, int max_wg, u st) {
+    if (key_cols.size() != classes.size()) return (int)hipErrorInvalidValue;
+    return hopsx_group_keys64(P<double>(x), rows, cols, key_cols.data(), classes.data(), (int)key_cols.size(),
+                              P<unsigned long long>(comp), P<unsigned long long>(keys), max_wg, S(st));
+  });
+  m.def("group_heads64", [](u keys, long rows, u heads, u seg_off, u first_row, u info, int max_wg, u st) {
+    return hopsx_group_heads64(P<unsigned long long>(keys), rows, P<unsigned>(heads), P<long long>(seg_off),
+                               P<long long>(first_row), P<long long>(info), max_wg, S(st));
+  });
+  m.def("group_reduce64", [](u x, long rows, int V, u keys, u seg_off, long G, u part, u count, u sum, u mn, u mx, u mean,
+                             u var, int max_wg, u st) {
+    return hopsx_group_reduce64(P<double>(x), rows, V, P<unsigned long long>(keys), P<long long>(seg_off), G,
+                                P<unsigned long long>(part), P<long long>(count), P<double>(sum), P<double>(mn),
+                                P<double>(mx), P<double>(mean), P<double>(var), max_wg, S(st));
+  });
+  m.def("group_tile", []() { return hopsx_group_tile(); });
+  m.def("group_col_block", []() { return hopsx_group_col_block(); });
+  m.def("group_part_words", [](long rows, int V) { return hopsx_group_part_words(rows, V); });
   m.def("u8_normalize_chan", [](u x, u y, long pixels, int C, std::vector<float> scale, std::vector<float> shift,
                                 int rev, int cout, u st) {
     if ((int)scale.size() < C || (int)shift.size() < C) return -2;

@@ -371,6 +371,27 @@ int hopsx_column_pair_ranks64(const double* x, long rows, int cols, const int* p
                               long long* dcount, unsigned long long* comp, int max_workgroups, hipStream_t st);
 int hopsx_column_pair_table_keys();
 long hopsx_column_pair_head_words(long rows, int cols);
+// ---- group-by aggregates over sorted group keys (groupagg.hip) ----
+// keys[r] = code << 32 | r: code the mixed-radix number of row r's ranks (the low words of comp uint64 [nkeys][rows],
+// hopsx_column_pair_ranks64 of the pairs (k, k)) in the key columns key_cols[nkeys] of x, classes[nkeys] their class
+// counts (both on the host), the first key most significant; 0xFFFFFFFF for a row with a NaN key.
+// hipErrorInvalidValue, nothing launched: nkeys outside 1..4, a class-count product >= 2^32 - 1, rows >= 2^31.
+int hopsx_group_keys64(const double* x, long rows, int cols, const int* key_cols, const long long* classes, int nkeys,
+                       const unsigned long long* comp, unsigned long long* keys, int max_workgroups, hipStream_t st);
+// keys sorted (hopsx_column_sort_keys64): seg_off int64 [rows + 1] and first_row int64 [rows] receive their first
+// G + 1 resp. G entries (seg_off[G] = the rows that are in a group), info int64 [2] = G, seg_off[G].  heads:
+// ceil(rows / hopsx_group_tile()) uint32.
+int hopsx_group_heads64(const unsigned long long* keys, long rows, unsigned* heads, long long* seg_off,
+                        long long* first_row, long long* info, int max_workgroups, hipStream_t st);
+// x fp64 [rows][V] (NaN skipped), the sorted keys and seg_off [G + 1] -> count int64 and sum, min, max, mean fp64,
+// each [G][V]; var (may be null) the sample variance from a second, centred pass.  part:
+// hopsx_group_part_words(rows, V) words.  Fixed-order sums: the same bits for any max_workgroups.
+int hopsx_group_reduce64(const double* x, long rows, int V, const unsigned long long* keys, const long long* seg_off,
+                         long G, unsigned long long* part, long long* count, double* sum, double* mn, double* mx,
+                         double* mean, double* var, int max_workgroups, hipStream_t st);
+int hopsx_group_tile();       // sorted positions per workgroup tile
+int hopsx_group_col_block();  // value columns staged in LDS at a time
+long hopsx_group_part_words(long rows, int V);
 // per-channel uint8 NHWC -> bf16 image normalisation (C <= 4, optional channel reversal)
 int hopsx_u8_normalize_chan(const unsigned char* x, void* y, long pixels, int C, const float* scale,
                             const float* shift, int rev, int cout, hipStream_t st);

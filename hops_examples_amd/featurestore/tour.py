@@ -71,12 +71,15 @@ def _stats():
 
 def _per_team(raw: pd.DataFrame, cols: dict) -> pd.DataFrame:
     """sum + count per team_id, averaged (the Spark groupBy().sum() join groupBy().count() of
-    ComputeFeatures.scala:148-160)."""
-    g = raw.groupby("team_id")
-    out = pd.DataFrame({"team_id": g.size().index.astype("int32")})
-    cnt = g.size().to_numpy().astype(np.float32)
+    ComputeFeatures.scala:148-160), through ``window.group_aggregates``: these frames are a few hundred rows, far
+    below any size at which it leaves the pandas route.  The count is the group's rows: that of the key itself."""
+    from .window import group_aggregates
+
+    agg, _ = group_aggregates(raw, "team_id", ["team_id", *cols], aggs=("count", "sum"))
+    out = pd.DataFrame({"team_id": agg.index.astype("int32")})
+    cnt = agg[("team_id", "count")].to_numpy().astype(np.float32)
     for src, (avg_name, sum_name) in cols.items():
-        s = g[src].sum().to_numpy().astype(np.float32)
+        s = agg[(src, "sum")].to_numpy().astype(np.float32)
         if avg_name:
             out[avg_name] = s / cnt
         if sum_name:

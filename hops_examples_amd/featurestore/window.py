@@ -10,6 +10,9 @@ on the GPU (``window.hip``: fp64 prefix sum + two binary searches per row and wi
 in one launch) when a GPU is present and the frame is large enough to pay for the copies, else
 through the same algorithm in numpy.  An empty range gives NaN (Spark's null) — fill as the
 reference does.  Result order is the input frame's order.
+
+``group_aggregates`` is the plain group-by beside them (``groupBy().sum()`` / ``count()`` / ``avg()``,
+``sales.groupby("store")``): pandas' own frame, from ``groupagg.hip`` for large numeric frames.
 """
 from __future__ import annotations
 
@@ -145,3 +148,84 @@ def with_range_sums(df: pd.DataFrame, specs: dict, partition_by, order_by: str, 
         col = sums[:, j]
         out[k] = np.where(np.isnan(col), fill, col) if fill is not None else col
     return out
+
+
+# ---- plain group-by: df.groupby(by, sort=True)[values].agg([...]) ----
+GROUP_AGGS = ("count", "sum", "mean", "min", "max", "std", "var")
+GROUP_MAX_KEYS = 4
+# Rows from which group_aggregates takes the device route on its own (None: only with device="cuda"): the smallest
+# measured size at which the device route won five of five alternating pairs against pandas at BOTH group counts
+# (tools/groupagg_bench.py on one MI355X, V = 4, upload included; profiles/r27_groupagg.txt):
+#   rows         groups    device      pandas     pairs won
+#   100,000          50      2.5 ms      4.7 ms   5 of 5
+#   100,000      63,106      5.1 ms     12.3 ms   5 of 5
+#   1,000,000        50     11.2 ms     33.2 ms   5 of 5
+#   1,000,000    99,995     15.9 ms     75.8 ms   5 of 5
+#   10,000,000       50     94.3 ms    309.5 ms   5 of 5
+#   10,000,000  100,000     98.7 ms    576.5 ms   5 of 5
+# Nothing below 100,000 rows has been measured.
+GROUP_GPU_MIN_ROWS = 100_000
+
+
+def group_aggregates(df: pd.DataFrame, by, values, aggs=("count", "sum", "mean", "min", "max"), device=None):
+    """``(df.groupby(by, sort=True)[values].agg(list(aggs)), route)``: the frame pandas returns (the key columns first,
+    as its index; one column per value and aggregate; a row with a missing key belongs to no group, a missing value is
+    skipped) and the route that computed it, 'gpu' (``groupagg.hip``: the keys' dense ranks, one sort of 64-bit group
+    keys, a segmented fixed-order reduction) or 'cpu' (that pandas line).  ``by`` / ``values``: a name or a list of
+    names.  The reference's ``groupBy().sum()`` / ``count()`` / ``avg()`` (ComputeFeatures.scala:148-160) and
+    ``sales.groupby("store")`` (feature_engineering.py).
+
+    The device route is taken with a GPU and ``device="cuda"``, or on its own from ``GROUP_GPU_MIN_ROWS`` rows.  It
+    declines, and pandas runs, for: a key or value column that is not numeric, is bool, or holds integers beyond 2^53
+    (an integer value column also when rows x max |v| could pass 2^53, where pandas' int64 sum is exact and fp64 is
+    not); more than 4 key columns; an aggregate outside ``GROUP_AGGS``; key columns whose class counts multiply to
+    2^32 - 1 or more; no group at all.  Integer value columns come back in pandas' dtypes."""
+    by = [by] if isinstance(by, str) else list(by)
+    values = [values] if isinstance(values, str) else list(values)
+    aggs = list(aggs)
+
+    def host():
+        return df.groupby(by, sort=True)[values].agg(aggs), "cpu"
+
+    use_gpu = False
+    if len(df) and by and values and len(by) <= GROUP_MAX_KEYS and all(a in GROUP_AGGS for a in aggs):
+        import torch
+
+        use_gpu = torch.cuda.is_available() and (
+            (device is not None and torch.device(device).type == "cuda")
+            or (device is None and GROUP_GPU_MIN_ROWS is not None and len(df) >= GROUP_GPU_MIN_ROWS))
+    if not use_gpu:
+        return host()
+    from .rules import order_eligible
+
+    if not all(order_eligible(df[c]) for c in dict.fromkeys(by + values)):
+        return host()
+    ints = [c for c in values if pd.api.types.is_integer_dtype(df[c].dtype)]
+    if any(max(abs(int(df[c].min())), abs(int(df[c].max()))) * len(df) >= 1 << 53 for c in ints):
+        return host()
+    import torch
+
+    from ..ops import kernels as K
+
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    x = np.stack([pd.to_numeric(df[c], errors="coerce").to_numpy(np.float64, na_value=np.nan) for c in by + values], 1)
+    xt = torch.from_numpy(np.ascontiguousarray(x)).pin_memory().to(dev, non_blocking=True)
+    nk = len(by)
+    try:
+        r = K.group_by64(xt, range(nk), range(nk, nk + len(values)), want_var="std" in aggs or "var" in aggs)
+    except K.GroupKeyRange:
+        return host()
+    if not r["G"]:
+        return host()
+    first = r["first_row"].cpu().numpy()
+    got = {a: r[a].cpu().numpy() for a in ("count", "sum", "mean", "min", "max", "var") if a in r}
+    if "var" in got:
+        got["std"] = np.sqrt(got["var"])
+    keys = [df[k].to_numpy()[first] for k in by]
+    index = pd.Index(keys[0], name=by[0]) if nk == 1 else pd.MultiIndex.from_arrays(keys, names=by)
+    data = {}
+    for j, v in enumerate(values):
+        for a in aggs:
+            col = got[a][:, j]
+            data[(v, a)] = col.astype(df[v].dtype) if v in ints and a in ("sum", "min", "max") else col
+    return pd.DataFrame(data, index=index), "gpu"

@@ -1626,6 +1626,49 @@ def column_pair_entropy_reference(x, pairs):
     return ent, counts
 
 
+def group_reference(x, key_cols, value_cols):
+    """The group-by aggregates of groupagg.hip stated on the host, from the fp64 array ``x`` [rows, cols]: the groups
+    are ``np.unique`` over the rows of the key columns (ascending, first key most significant; -0.0 as +0.0; a row with
+    a NaN key is dropped), and per group and value column, NaN skipped: ``count``, ``sum`` (``math.fsum``; 0.0 without a
+    value), ``min``, ``max``, ``mean`` = fsum / count and ``var`` (the sample variance, centred and summed in
+    ``np.longdouble``, rounded once), NaN without a value (``var``: below two).  Returns a dict of those [G, V] arrays
+    plus ``keys`` fp64 [G, K], ``seg_off`` int64 [G + 1] (the groups' extents in sorted order), ``first_row`` int64 [G]
+    (the smallest row of every group) and ``dropped``."""
+    import math
+
+    import numpy as np
+
+    a = _as_f64_2d(x)
+    kc, vc = [int(c) for c in key_cols], [int(c) for c in value_cols]
+    k = a[:, kc] + 0.0
+    kept = np.flatnonzero(~np.isnan(k).any(1))
+    uniq, inv = np.unique(k[kept], axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    G, V = len(uniq), len(vc)
+    by_group = kept[np.argsort(inv, kind="stable")]
+    seg_off = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=G))]).astype(np.int64)
+    out = {"count": np.zeros((G, V), np.int64), "sum": np.zeros((G, V))}
+    out.update({q: np.full((G, V), np.nan) for q in ("min", "max", "mean", "var")})
+    for g in range(G):
+        r = by_group[seg_off[g]:seg_off[g + 1]]
+        for j, c in enumerate(vc):
+            v = a[r, c]
+            v = v[~np.isnan(v)]
+            if not v.size:
+                continue
+            s = math.fsum(v.tolist())
+            out["count"][g, j], out["sum"][g, j], out["mean"][g, j] = v.size, s, s / v.size
+            out["min"][g, j], out["max"][g, j] = v.min(), v.max()
+            if v.size > 1:
+                with np.errstate(invalid="ignore", over="ignore"):
+                    ld = v.astype(np.longdouble)
+                    d = ld - ld.sum() / v.size
+                    out["var"][g, j] = float(((d * d).sum() - d.sum() ** 2 / v.size) / (v.size - 1))
+    first_row = np.array([by_group[seg_off[g]] for g in range(G)], np.int64)
+    out.update(keys=uniq.reshape(G, len(kc)), seg_off=seg_off, first_row=first_row, dropped=int(a.shape[0] - kept.size))
+    return out
+
+
 def column_quantile_reference(x, qs):
     """fp64 [cols, len(qs)]: ``np.nanquantile`` of every column of ``x`` [rows, cols] (NaN for an empty column)."""
     import warnings

@@ -1277,6 +1277,141 @@ def column_pair_entropy64(x, pairs, max_workgroups=0, ws_cap_bytes=0, return_cou
     return (ent, cnt) if return_counts else ent
 
 
+# ------------------------------------------------------- group-by aggregates
+GROUP_MAX_KEYS = 4
+GROUP_DROP_CODE = 0xFFFFFFFF  # the code of a row with a NaN key; every group's code is below it
+
+
+class GroupKeyRange(ValueError):
+    """The key columns' class counts multiply to 2^32 - 1 or more: the group code does not fit its 32 bits."""
+
+
+def group_tile() -> int:
+    """Sorted positions per workgroup tile of the group-by kernels (csrc/ops/groupagg.hip)."""
+    return int(_C.ext().group_tile())
+
+
+def group_col_block() -> int:
+    """Value columns ``group_aggregate64`` stages in LDS at a time; more columns are taken block by block."""
+    return int(_C.ext().group_col_block())
+
+
+def _group_cols(cols_arg, cols, what, name):
+    import numpy as np
+
+    c = np.asarray(cols_arg.detach().cpu().numpy() if isinstance(cols_arg, torch.Tensor) else list(cols_arg))
+    if c.ndim != 1 or (c.size and not np.issubdtype(c.dtype, np.integer)):
+        raise ValueError(f"{what}: {name} must be a list of column indices")
+    if c.size and (c.min() < 0 or c.max() >= cols):
+        raise ValueError(f"{what}: {name} out of range for {cols} columns")
+    return [int(v) for v in c]
+
+
+def group_keys64(x, key_cols, order):
+    """int64 [1, rows]: per row of ``x`` (fp64 [rows, cols] on the GPU) the uint64 sort key ``code << 32 | row``, code
+    the mixed-radix number of the row's dense ranks in the 1..4 columns ``key_cols`` (first key most significant), so
+    ascending codes are pandas' ``sort=True`` group order; a row with a NaN key gets ``GROUP_DROP_CODE`` and sorts last.
+    ``order``: ``column_sort64(x)``.  Every refusal (more than 4 keys, a product of the columns' class counts of
+    2^32 - 1 or more) is a ValueError raised before group_keys_k is launched."""
+    rows, cols, _ = _pair_args(x, [], order.max_workgroups, "group_keys64")
+    kc = _group_cols(key_cols, cols, "group_keys64", "key_cols")
+    if not 1 <= len(kc) <= GROUP_MAX_KEYS:
+        raise ValueError(f"group_keys64: 1..{GROUP_MAX_KEYS} key columns expected, got {len(kc)}")
+    keys = torch.empty(1, rows, device=x.device, dtype=torch.int64)
+    if rows:
+        comp, dcount = column_pair_ranks64(x, [(k, k) for k in kc], order)
+        classes = [int(v) for v in dcount.cpu()[kc].tolist()]
+        prod = 1
+        for d in classes:
+            prod *= d
+        if prod >= GROUP_DROP_CODE:
+            raise GroupKeyRange(f"group_keys64: the key columns' class counts {classes} multiply to {prod} >= 2^32 - 1")
+        check(_C.ext().group_keys64(ptr(x), rows, cols, kc, classes, ptr(comp), ptr(keys), order.max_workgroups,
+                                    stream()), "group_keys64")
+    return keys
+
+
+def _group_keys_arg(keys_sorted, what):
+    if not isinstance(keys_sorted, torch.Tensor) or keys_sorted.dtype != torch.int64 or keys_sorted.dim() != 2 \
+            or keys_sorted.shape[0] != 1 or not keys_sorted.is_cuda or not keys_sorted.is_contiguous():
+        raise ValueError(f"{what}: keys_sorted must be a contiguous int64 [1, rows] GPU tensor")
+    return _sort_dims(keys_sorted.shape[1], 1, 0, what)[0]
+
+
+def group_segments64(keys_sorted, max_workgroups=0):
+    """``(seg_off int64 [G + 1], first_row int64 [G], G, dropped)`` of the sorted group keys (``group_keys64`` through
+    ``column_sort_keys64``): group g is the sorted positions ``seg_off[g]..seg_off[g + 1]``, ``first_row[g]`` its
+    smallest row, ``dropped`` the rows with a NaN key (the tail behind ``seg_off[G]``).  Reading G waits for the
+    kernels."""
+    rows = _group_keys_arg(keys_sorted, "group_segments64")
+    if int(max_workgroups) < 0:
+        raise ValueError("group_segments64: max_workgroups >= 0 expected")
+    dev = keys_sorted.device
+    if not rows:
+        return torch.zeros(1, device=dev, dtype=torch.int64), torch.zeros(0, device=dev, dtype=torch.int64), 0, 0
+    T = group_tile()
+    seg_off = torch.empty(rows + 1, device=dev, dtype=torch.int64)
+    first_row = torch.empty(rows, device=dev, dtype=torch.int64)
+    info = torch.empty(2, device=dev, dtype=torch.int64)
+    heads = torch.empty((rows + T - 1) // T, device=dev, dtype=torch.int32)
+    check(_C.ext().group_heads64(ptr(keys_sorted), rows, ptr(heads), ptr(seg_off), ptr(first_row), ptr(info),
+                                 int(max_workgroups), stream()), "group_heads64")
+    G, kept = (int(v) for v in info.cpu().tolist())
+    return seg_off[:G + 1].clone(), first_row[:G].clone(), G, rows - kept
+
+
+def group_aggregate64(x, value_cols, keys_sorted, seg_off, want_var=False, max_workgroups=0):
+    """Per group of the sorted keys and per column of ``value_cols`` of ``x`` (fp64 [rows, cols] on the GPU, NaN
+    skipped): a dict of ``count`` int64 [G, V] and ``sum``, ``min``, ``max``, ``mean`` (and ``var``, the sample
+    variance from a second, centred pass, with ``want_var``) fp64 [G, V].  A group without a value has count 0, sum
+    0.0 and NaN elsewhere; ``var`` is NaN below two values.  Any number of columns: the kernel walks them in blocks of
+    ``group_col_block()``.  Fixed-order sums: the same bits for any ``max_workgroups``.  Every refusal is a ValueError
+    raised before any launch."""
+    rows, cols, _ = _pair_args(x, [], max_workgroups, "group_aggregate64")
+    vc = _group_cols(value_cols, cols, "group_aggregate64", "value_cols")
+    if _group_keys_arg(keys_sorted, "group_aggregate64") != rows or keys_sorted.device != x.device:
+        raise ValueError(f"group_aggregate64: keys_sorted must hold the {rows} rows of x on {x.device}")
+    if not isinstance(seg_off, torch.Tensor) or seg_off.dtype != torch.int64 or seg_off.dim() != 1 \
+            or not 1 <= seg_off.numel() <= rows + 1 or seg_off.device != x.device or not seg_off.is_contiguous():
+        raise ValueError(f"group_aggregate64: seg_off must be a contiguous int64 [G + 1] tensor, G <= {rows}, on {x.device}")
+    G, V = seg_off.numel() - 1, len(vc)
+    f64 = lambda fill: torch.full((G, V), fill, device=x.device, dtype=torch.float64)  # noqa: E731
+    out = {"count": torch.zeros(G, V, device=x.device, dtype=torch.int64), "sum": f64(0.0), "min": f64(float("nan")),
+           "max": f64(float("nan")), "mean": f64(float("nan"))}
+    if want_var:
+        out["var"] = f64(float("nan"))
+    if rows and G and V:
+        ext = _C.ext()
+        xv = x if vc == list(range(cols)) else x[:, torch.tensor(vc, device=x.device)].contiguous()
+        part = torch.empty(int(ext.group_part_words(rows, V)), device=x.device, dtype=torch.int64)
+        check(ext.group_reduce64(ptr(xv), rows, V, ptr(keys_sorted), ptr(seg_off), G, ptr(part), ptr(out["count"]),
+                                 ptr(out["sum"]), ptr(out["min"]), ptr(out["max"]), ptr(out["mean"]),
+                                 ptr(out["var"]) if want_var else 0, int(max_workgroups), stream()), "group_reduce64")
+    return out
+
+
+def group_by64(x, key_cols, value_cols, want_var=False, max_workgroups=0, ws_cap_bytes=0):
+    """``x.groupby(key_cols, sort=True, dropna=True)[value_cols]`` on the device (csrc/ops/groupagg.hip): the key
+    columns sorted (``column_sort64``), every row's dense ranks (``column_pair_ranks64``), the group keys
+    (``group_keys64``) sorted by the same digit passes (``column_sort_keys64``), their runs (``group_segments64``) and
+    the aggregates (``group_aggregate64``).  Returns that dict plus ``seg_off``, ``first_row`` (a row of every group,
+    for its key values), ``G`` and ``dropped``.  -0.0 and +0.0 are one key."""
+    rows, cols, _ = _pair_args(x, [], max_workgroups, "group_by64")
+    kc = _group_cols(key_cols, cols, "group_by64", "key_cols")
+    _group_cols(value_cols, cols, "group_by64", "value_cols")
+    if not 1 <= len(kc) <= GROUP_MAX_KEYS:
+        raise ValueError(f"group_by64: 1..{GROUP_MAX_KEYS} key columns expected, got {len(kc)}")
+    _sort_dims(rows, len(kc), ws_cap_bytes, "group_by64")
+    xk = x[:, torch.tensor(kc, device=x.device)].contiguous()
+    order = column_sort64(xk, max_workgroups=max_workgroups, ws_cap_bytes=ws_cap_bytes)
+    keys = group_keys64(xk, list(range(len(kc))), order)
+    column_sort_keys64(keys, max_workgroups=max_workgroups, ws_cap_bytes=ws_cap_bytes)
+    seg_off, first_row, G, dropped = group_segments64(keys, max_workgroups=max_workgroups)
+    out = group_aggregate64(x, value_cols, keys, seg_off, want_var=want_var, max_workgroups=max_workgroups)
+    out.update(seg_off=seg_off, first_row=first_row, G=G, dropped=dropped)
+    return out
+
+
 def column_hist(x, mins, maxs, bins):
     rows, cols = x.shape
     hist = torch.zeros(cols, bins, device=x.device, dtype=torch.int32)
