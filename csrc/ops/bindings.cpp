@@ -50,7 +50,7 @@ static inline hipStream_t S(u s) { return reinterpret_cast<hipStream_t>(s); }
 #define HOPSX_DET_TUS(X) \
   X(conv_mfma) X(loss) X(gemm) X(norm) X(pool) X(conv) X(elementwise) X(rowreduce) X(wgrad_glds)
 #define HOPSX_DBG_TUS(X) HOPSX_DET_TUS(X) X(embedding) X(mnist_eval) X(cnn_eval) X(taxi_eval) X(topk) X(colsort) \
-  X(colpair) X(groupagg)
+  X(colpair) X(groupagg) X(join)
 #define X(tag)                             \
   extern "C" int hopsx_det_set_##tag(int);  \
   extern "C" unsigned hopsx_det_lost_##tag();
@@ -582,6 +582,31 @@ HX_PYMOD(HOPSX_MODNAME) {
   m.def("group_tile", []() { return hopsx_group_tile(); });
   m.def("group_col_block", []() { return hopsx_group_col_block(); });
   m.def("group_part_words", [](long rows, int V) { return hopsx_group_part_words(rows, V); });
+  m.def("join_tile", []() { return hopsx_join_tile(); });
+  m.def("join_table_rows", []() { return hopsx_join_table_rows(); });
+  m.def("join_spans64", [](u keys, long nl, long nr, u heads, u seg_off, u first_row, u ginfo, u split, u rbeg, u rcnt,
+                           u lcnt, int max_wg, u st) {
+    return hopsx_join_spans64(P<unsigned long long>(keys), nl, nr, P<unsigned>(heads), P<long long>(seg_off),
+                              P<long long>(first_row), P<long long>(ginfo), P<long long>(split), P<int>(rbeg),
+                              P<unsigned>(rcnt), P<unsigned>(lcnt), max_wg, S(st));
+  });
+  m.def("join_offsets64", [](u cnt, long m_, int mode, u tot, u nz, u off, u info, int max_wg, u st) {
+    return hopsx_join_offsets64(P<unsigned>(cnt), m_, mode, P<unsigned long long>(tot), P<unsigned>(nz),
+                                P<long long>(off), P<long long>(info), max_wg, S(st));
+  });
+  m.def("join_expand64", [](u keys, long nl, long nr, u off, u rbeg, u rcnt, long n_main, u li, u ri, int max_wg, u st) {
+    return hopsx_join_expand64(P<unsigned long long>(keys), nl, nr, P<long long>(off), P<int>(rbeg), P<unsigned>(rcnt),
+                               n_main, P<int>(li), P<int>(ri), max_wg, S(st));
+  });
+  m.def("join_tail64", [](u lcnt, long nr, u tot, long base, long n_out, u li, u ri, int max_wg, u st) {
+    return hopsx_join_tail64(P<unsigned>(lcnt), nr, P<unsigned long long>(tot), base, n_out, P<int>(li), P<int>(ri),
+                             max_wg, S(st));
+  });
+  m.def("join_gather64", [](u xl, long nl, int colsl, u xr, long nr, int colsr, u li, u ri, long n_out, u cols, int CL,
+                            int CR, u out, int max_wg, u st) {
+    return hopsx_join_gather64(P<double>(xl), nl, colsl, P<double>(xr), nr, colsr, P<int>(li), P<int>(ri), n_out,
+                               P<int>(cols), CL, CR, P<double>(out), max_wg, S(st));
+  });
   m.def("u8_normalize_chan", [](u x, u y, long pixels, int C, std::vector<float> scale, std::vector<float> shift,
                                 int rev, int cout, u st) {
     if ((int)scale.size() < C || (int)shift.size() < C) return -2;

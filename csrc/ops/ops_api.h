@@ -392,6 +392,37 @@ int hopsx_group_reduce64(const double* x, long rows, int V, const unsigned long 
 int hopsx_group_tile();       // sorted positions per workgroup tile
 int hopsx_group_col_block();  // value columns staged in LDS at a time
 long hopsx_group_part_words(long rows, int V);
+// ---- equi-joins over the sorted stacked keys of two frames (join.hip) ----
+// keys uint64 [nl + nr]: hopsx_group_keys64 of the left frame's key columns stacked over the right frame's, sorted
+// (hopsx_column_sort_keys64): row < nl is a left row.  _spans64 runs hopsx_group_heads64 (heads, seg_off, first_row,
+// ginfo as there) and writes split int64 [nl + nr] (per run, its first right position), per left row rbeg int32 [nl]
+// (the sorted position of its run's first right row) and rcnt uint32 [nl] (its run's right rows; 0 for a NaN key), per
+// right row lcnt uint32 [nr] (its run's left rows).  nl, nr >= 1, nl + nr < 2^31.
+int hopsx_join_spans64(const unsigned long long* keys, long nl, long nr, unsigned* heads, long long* seg_off,
+                       long long* first_row, long long* ginfo, long long* split, int* rbeg, unsigned* rcnt,
+                       unsigned* lcnt, int max_workgroups, hipStream_t st);
+// the exclusive 64-bit scan of f(cnt[i]), i < m, in three launches (tile totals, one workgroup over them, tile-local):
+// mode 0 f = cnt, 1 max(cnt, 1), 2 cnt == 0.  tot uint64 / nz uint32 [ceil(m / hopsx_join_tile())]: tot is left
+// holding the scanned tile totals.  off int64 [m + 1] (off[m] = the total) or null: no tile-local launch.
+// info int64 [2] = the total, the rows with cnt > 0.
+int hopsx_join_offsets64(const unsigned* cnt, long m, int mode, unsigned long long* tot, unsigned* nz, long long* off,
+                         long long* info, int max_workgroups, hipStream_t st);
+// li / ri int32 [n_main] from off [nl + 1] (n_main = off[nl] < 2^31): left row order, within a left row right row
+// order; ri = -1 for a left row without a match (off from mode 1).  A workgroup owns hopsx_join_tile() output positions
+// and stages the covering rows' offsets in LDS in chunks of hopsx_join_table_rows().
+int hopsx_join_expand64(const unsigned long long* keys, long nl, long nr, const long long* off, const int* rbeg,
+                        const unsigned* rcnt, long n_main, int* li, int* ri, int max_workgroups, hipStream_t st);
+// the full join's tail: the right rows with lcnt == 0 in row order to li / ri [base, n_out) as (-1, row); tot: the
+// scanned tile totals hopsx_join_offsets64(lcnt, nr, 2, ...) left
+int hopsx_join_tail64(const unsigned* lcnt, long nr, const unsigned long long* tot, long base, long n_out, int* li,
+                      int* ri, int max_workgroups, hipStream_t st);
+// out fp64 [n_out][CL + CR]: xl[li[t]][cols[c]] for c < CL, xr[ri[t]][cols[c]] behind them, NaN where the index is -1
+// (bits copied, a NaN payload survives); cols int32 [CL + CR] on the device
+int hopsx_join_gather64(const double* xl, long nl, int colsl, const double* xr, long nr, int colsr, const int* li,
+                        const int* ri, long n_out, const int* cols, int CL, int CR, double* out, int max_workgroups,
+                        hipStream_t st);
+int hopsx_join_tile();        // output positions per workgroup tile of the expand
+int hopsx_join_table_rows();  // offsets one LDS chunk of the expand holds
 // per-channel uint8 NHWC -> bf16 image normalisation (C <= 4, optional channel reversal)
 int hopsx_u8_normalize_chan(const unsigned char* x, void* y, long pixels, int C, const float* scale,
                             const float* shift, int rev, int cout, hipStream_t st);

@@ -340,6 +340,13 @@ class Query:
         for fg in self._fgs():
             q = self if fg is self._left_fg else next(j.query for j in self._joins if j.query._left_fg is fg)
             frames[fg._table] = fg._read_df(online=online, as_of=q._as_of)
+        # joined queries without sqlite's per-row inserts (featurestore/join.py); every decline runs the SQL line
+        from .join import read_query
+
+        out, self.last_read_route = read_query(self, frames, device=(read_options or {}).get("join_device"))
+        if out is not None:
+            return out
+        self.last_read_route = "sql: " + self.last_read_route
         return fs._run_sql(self.to_string(online), frames)
 
     def show(self, n: int = 20, online: bool = False) -> None:

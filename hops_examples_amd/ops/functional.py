@@ -1669,6 +1669,39 @@ def group_reference(x, key_cols, value_cols):
     return out
 
 
+def join_reference(xl, xr, left_keys, right_keys, how="inner"):
+    """The equi-join of join.hip stated on the host: ``(li, ri)`` int64 arrays of the row pairs of
+    ``xl JOIN xr ON xl[left_keys] = xr[right_keys]`` (fp64 arrays; a NaN key matches nothing, -0.0 is +0.0), ``how``
+    inner, left or full.  A dict from key tuple to the list of right rows, walked in left row order: left row order,
+    within a left row right row order, -1 for the missing side; for full the unmatched right rows follow in row
+    order."""
+    import numpy as np
+
+    if how not in ("inner", "left", "full"):
+        raise ValueError(f"join_reference: how must be inner, left or full, got {how!r}")
+    a, b = _as_f64_2d(xl), _as_f64_2d(xr)
+    ka, kb = a[:, [int(c) for c in left_keys]] + 0.0, b[:, [int(c) for c in right_keys]] + 0.0
+    if ka.shape[1] != kb.shape[1]:
+        raise ValueError("join_reference: key counts differ")
+    table = {}
+    for r in np.flatnonzero(~np.isnan(kb).any(1)):
+        table.setdefault(tuple(kb[r].tolist()), []).append(int(r))
+    li, ri = [], []
+    seen = np.zeros(len(b), bool)
+    for l in range(len(a)):
+        rows = [] if np.isnan(ka[l]).any() else table.get(tuple(ka[l].tolist()), [])
+        seen[rows] = True
+        if not rows and how != "inner":
+            rows = [-1]
+        li += [l] * len(rows)
+        ri += rows
+    if how == "full":
+        rest = np.flatnonzero(~seen).tolist()
+        li += [-1] * len(rest)
+        ri += rest
+    return np.asarray(li, np.int64), np.asarray(ri, np.int64)
+
+
 def column_quantile_reference(x, qs):
     """fp64 [cols, len(qs)]: ``np.nanquantile`` of every column of ``x`` [rows, cols] (NaN for an empty column)."""
     import warnings

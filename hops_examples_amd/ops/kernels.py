@@ -1412,6 +1412,129 @@ def group_by64(x, key_cols, value_cols, want_var=False, max_workgroups=0, ws_cap
     return out
 
 
+# ------------------------------------------------------- equi-joins
+JOIN_KINDS = ("inner", "left", "full")
+
+
+class JoinTooLarge(ValueError):
+    """The join has 2^31 or more result rows: ``li`` / ``ri`` are int32."""
+
+
+def join_tile() -> int:
+    """Output positions per workgroup tile of the join's expand (csrc/ops/join.hip)."""
+    return int(_C.ext().join_tile())
+
+
+def join_table_rows() -> int:
+    """Left-row offsets one LDS chunk of the join's expand holds; a tile that covers more rows walks them in chunks."""
+    return int(_C.ext().join_table_rows())
+
+
+def _join_side(x, what, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{what}: {name} [rows, cols] expected")
+    if x.dtype != torch.float64:
+        raise ValueError(f"{what}: fp64 expected, got {x.dtype} for {name}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: expected a GPU tensor for {name}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous tensor for {name}")
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def join_pairs64(xl, xr, left_keys, right_keys, how="inner", max_workgroups=0, ws_cap_bytes=0):
+    """The row pairs of ``xl JOIN xr ON xl[left_keys] = xr[right_keys]`` (fp64 [rows, cols] on the GPU, NaN = NULL: a
+    NaN key matches nothing; -0.0 and +0.0 are one key), ``how`` inner, left or full: a dict of ``li`` / ``ri`` int32
+    [n_out] (-1: no row on that side), ``n_out``, ``matched_left`` and ``matched_right`` (the rows of either side with
+    a partner).  Order: left row order, within a left row right row order, then (full) the unmatched right rows in row
+    order.  The key columns of both sides are stacked and ranked (``column_sort64``, ``group_keys64``), the stacked
+    keys sorted (``column_sort_keys64``), and csrc/ops/join.hip turns the runs into spans, offsets and pairs; ``n_out``
+    is read on the host to allocate them.  Integers only: the same result for any ``max_workgroups`` and
+    ``ws_cap_bytes``.  Every refusal is a ValueError raised before the launch it concerns: ``GroupKeyRange`` from
+    ``group_keys64``, ``JoinTooLarge`` for n_out >= 2^31."""
+    what = "join_pairs64"
+    nl, cl = _join_side(xl, what, "xl")
+    nr, cr = _join_side(xr, what, "xr")
+    if xl.device != xr.device:
+        raise ValueError(f"{what}: xl and xr must be on one device")
+    lk, rk = _group_cols(left_keys, cl, what, "left_keys"), _group_cols(right_keys, cr, what, "right_keys")
+    if len(lk) != len(rk):
+        raise ValueError(f"{what}: {len(lk)} left keys against {len(rk)} right keys")
+    if not 1 <= len(lk) <= GROUP_MAX_KEYS:
+        raise ValueError(f"{what}: 1..{GROUP_MAX_KEYS} key columns expected, got {len(lk)}")
+    if how not in JOIN_KINDS:
+        raise ValueError(f"{what}: how must be one of {JOIN_KINDS}, got {how!r}")
+    if int(max_workgroups) < 0:
+        raise ValueError(f"{what}: max_workgroups >= 0 expected")
+    n, mw, dev = nl + nr, int(max_workgroups), xl.device
+    _sort_dims(n, len(lk), ws_cap_bytes, what)
+    if n >= 1 << 31:
+        raise ValueError(f"{what}: nl + nr < 2^31 expected, got {n}")
+    if nl == 0 or nr == 0:  # nothing matches: no launch
+        keep_l, keep_r = (nl if how != "inner" else 0), (nr if how == "full" else 0)
+        li = torch.cat([torch.arange(keep_l, dtype=torch.int32), torch.full((keep_r,), -1, dtype=torch.int32)])
+        ri = torch.cat([torch.full((keep_l,), -1, dtype=torch.int32), torch.arange(keep_r, dtype=torch.int32)])
+        return {"li": li.to(dev), "ri": ri.to(dev), "n_out": keep_l + keep_r, "matched_left": 0, "matched_right": 0}
+    ext = _C.ext()
+    T = join_tile()
+    with torch.cuda.device(dev):
+        xk = torch.cat([xl[:, torch.tensor(lk, device=dev)], xr[:, torch.tensor(rk, device=dev)]], 0).contiguous()
+        order = column_sort64(xk, max_workgroups=mw, ws_cap_bytes=ws_cap_bytes)
+        keys = group_keys64(xk, list(range(len(lk))), order)
+        column_sort_keys64(keys, max_workgroups=mw, ws_cap_bytes=ws_cap_bytes)
+        i64 = lambda m: torch.empty(m, device=dev, dtype=torch.int64)  # noqa: E731
+        i32 = lambda m: torch.empty(m, device=dev, dtype=torch.int32)  # noqa: E731
+        seg_off, first_row, split, ginfo = i64(n + 1), i64(n), i64(n), i64(2)
+        heads = i32((n + group_tile() - 1) // group_tile())
+        rbeg, rcnt, lcnt = i32(nl), i32(nl), i32(nr)
+        check(ext.join_spans64(ptr(keys), nl, nr, ptr(heads), ptr(seg_off), ptr(first_row), ptr(ginfo), ptr(split),
+                               ptr(rbeg), ptr(rcnt), ptr(lcnt), mw, stream()), "join_spans64")
+        off, info = i64(nl + 1), i64(4)
+        tot_l, nz_l = i64((nl + T - 1) // T), i32((nl + T - 1) // T)
+        tot_r, nz_r = i64((nr + T - 1) // T), i32((nr + T - 1) // T)
+        check(ext.join_offsets64(ptr(rcnt), nl, 0 if how == "inner" else 1, ptr(tot_l), ptr(nz_l), ptr(off), ptr(info),
+                                 mw, stream()), "join_offsets64")
+        check(ext.join_offsets64(ptr(lcnt), nr, 2, ptr(tot_r), ptr(nz_r), 0, ptr(info[2:]), mw, stream()),
+              "join_offsets64")
+        n_main, matched_left, unmatched_right, matched_right = (int(v) for v in info.cpu().tolist())
+        n_out = n_main + (unmatched_right if how == "full" else 0)
+        if n_out >= 1 << 31:
+            raise JoinTooLarge(f"{what}: {n_out} result rows >= 2^31")
+        li, ri = i32(n_out), i32(n_out)
+        check(ext.join_expand64(ptr(keys), nl, nr, ptr(off), ptr(rbeg), ptr(rcnt), n_main, ptr(li), ptr(ri), mw,
+                                stream()), "join_expand64")
+        if how == "full":
+            check(ext.join_tail64(ptr(lcnt), nr, ptr(tot_r), n_main, n_out, ptr(li), ptr(ri), mw, stream()),
+                  "join_tail64")
+    return {"li": li, "ri": ri, "n_out": n_out, "matched_left": matched_left, "matched_right": matched_right}
+
+
+def join_gather64(xl, xr, li, ri, cols_l, cols_r, max_workgroups=0):
+    """fp64 [n_out, CL + CR]: the columns ``cols_l`` of ``xl`` at the rows ``li`` beside the columns ``cols_r`` of
+    ``xr`` at the rows ``ri`` (int32 [n_out] on the GPU, ``join_pairs64``'s), NaN where the index is -1.  Bits are
+    copied: a NaN payload comes through unchanged.  Every refusal is a ValueError raised before the launch."""
+    what = "join_gather64"
+    nl, cl = _join_side(xl, what, "xl")
+    nr, cr = _join_side(xr, what, "xr")
+    lc, rc = _group_cols(cols_l, cl, what, "cols_l"), _group_cols(cols_r, cr, what, "cols_r")
+    for t, name in ((li, "li"), (ri, "ri")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.device != xl.device \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int32 [n_out] tensor on {xl.device}")
+    if xr.device != xl.device or li.numel() != ri.numel() or int(max_workgroups) < 0:
+        raise ValueError(f"{what}: one device, li and ri of one length and max_workgroups >= 0 expected")
+    if len(lc) > 0xFFFF or len(rc) > 0xFFFF:
+        raise ValueError(f"{what}: at most 65535 columns per side")
+    n_out = li.numel()
+    out = torch.empty(n_out, len(lc) + len(rc), device=xl.device, dtype=torch.float64)
+    if n_out and lc + rc:
+        with torch.cuda.device(xl.device):
+            cols = torch.tensor(lc + rc, dtype=torch.int32).to(xl.device)
+            check(_C.ext().join_gather64(ptr(xl), nl, cl, ptr(xr), nr, cr, ptr(li), ptr(ri), n_out, ptr(cols), len(lc),
+                                         len(rc), ptr(out), int(max_workgroups), stream()), "join_gather64")
+    return out
+
+
 def column_hist(x, mins, maxs, bins):
     rows, cols = x.shape
     hist = torch.zeros(cols, bins, device=x.device, dtype=torch.int32)
